@@ -19,12 +19,24 @@ own P pairs; pairs partition embarrassingly, no data-path
 collective in this workload.  value = whole-job pairs/s (all ranks), MAX-over-
 ranks timing.
 
-Prints ONE JSON line from rank 0, including:
+A plain run sets up, warms up, times --steps passes and prints ONE JSON line
+from rank 0 (value, ms_per_step, ...), including:
  - roofline: dominant-kernel (k_tiles intersect) HIP-event time on the
-   engine's stream, algorithmic bytes = 8*(n+m+|out|) per pair; traffic from
+   engine's stream (recorded inside the timed passes, no run of its own),
+   algorithmic bytes = 8*(n+m+|out|) per pair; traffic from
    profiles/hbm_traffic.json (rocprofv3 PMC, collected separately) or null.
+
+--full adds everything that costs time outside the steps:
+ - the planted-overlap sanity check of the timed path's output,
  - cpu_baseline: the oracle (C restatement of algo/uidlist.go, OpenMP across
    pairs) timed on this box's host cores over a bounded sample ("port").
+Without --full, cpu_baseline is null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(rank 0's batch): DIR/lens.npy (per-pair output length) and DIR/out.npy (the
+valid prefix of every pair's output list, concatenated in pair order), both
+float64.  Inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 """
 import argparse
 import json
@@ -42,6 +54,7 @@ LIST_LEN = 1_000_000
 OVERLAP = 10_000
 LIMIT = 100_000_000
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs budget over all arrays
 
 
 def log(msg):
@@ -97,6 +110,30 @@ def cpu_baseline(us_np, vs_np, target_seconds):
     }
 
 
+def dump_outputs(path, outs, lens):
+    """Write the last timed step's results as float64 .npy files.  UIDs of
+    this workload are < 2^53, so float64 holds them exactly.  If the
+    concatenated output exceeds the byte budget, a fixed seeded sample of its
+    elements (ascending positions) is written instead."""
+    import torch
+
+    from dgraph_amd import synth
+
+    os.makedirs(path, exist_ok=True)
+    lens_a = np.asarray(lens, dtype=np.float64)
+    cat = torch.cat([o[:n] for o, n in zip(outs, lens)])
+    cap = (DUMP_MAX_BYTES - lens_a.nbytes) // 8
+    if cat.numel() > cap:
+        idx = np.sort(np.random.default_rng(synth.SEED).choice(
+            cat.numel(), size=cap, replace=False))
+        cat = cat[torch.from_numpy(idx).to(cat.device)]
+    out_u = cat.cpu().numpy().view(np.uint64)
+    assert out_u.size == 0 or int(out_u.max()) < (1 << 53), \
+        "dump: uid not exactly representable in float64"
+    np.save(os.path.join(path, "lens.npy"), lens_a)
+    np.save(os.path.join(path, "out.npy"), out_u.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -105,7 +142,11 @@ def main():
     ap.add_argument("--pairs", type=int, default=192,
                     help="1Mx1M list pairs resident per GPU")
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
-                    help="CPU-baseline sample duration (0 disables)")
+                    help="CPU-baseline sample duration under --full (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the output sanity check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -136,21 +177,18 @@ def main():
     for p in range(P):
         gp = rank * P + p
         up, vp, _ = synth.offset_pair(u0, v0, common0, gp)
-        us_np.append(up)
-        vs_np.append(vp)
+        if args.full:  # host copies feed the CPU baseline only
+            us_np.append(up)
+            vs_np.append(vp)
         us.append(torch.from_numpy(up.view(np.int64)).to(dev))
         vs.append(torch.from_numpy(vp.view(np.int64)).to(dev))
     outs = [torch.empty(LIST_LEN, dtype=torch.int64, device=dev) for _ in range(P)]
     # prepared batch: descriptors + merge-path partition once, runs = launches
     batch = eng.make_batch(us, vs, outs)
 
-    # ---- warmup + correctness sanity (planted overlap) ----
+    # ---- warmup ----
     for _ in range(args.warmup):
-        lens = batch.run(algo.OP_INTERSECT)
-    got0 = outs[0][:lens[0]].cpu().numpy().view(np.uint64)
-    want0 = common0 + (np.uint64(rank * P) << np.uint64(32))
-    assert lens[0] == OVERLAP and np.array_equal(got0, want0), \
-        "bench sanity check failed: intersect output != planted overlap"
+        batch.run(algo.OP_INTERSECT)
 
     # ---- timed region: barrier + sync both sides, MAX over ranks ----
     if distributed:
@@ -161,7 +199,7 @@ def main():
     t0 = time.perf_counter()
     # K passes enqueued back-to-back, one sync (ua_batch_run_n): the serving
     # shape — each step is still one full pass of the hot path over the batch
-    batch.run_n(algo.OP_INTERSECT, args.steps)
+    lens = batch.run_n(algo.OP_INTERSECT, args.steps)
     torch.cuda.synchronize()
     if distributed:
         import torch.distributed as dist
@@ -199,8 +237,18 @@ def main():
             "launches_sampled": stats["launches"],
         }
 
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, outs, lens)
+
+    # ---- correctness sanity (planted overlap) of the timed path's output ----
+    if args.full and args.steps > 0:
+        got0 = outs[0][:lens[0]].cpu().numpy().view(np.uint64)
+        want0 = common0 + (np.uint64(rank * P) << np.uint64(32))
+        assert lens[0] == OVERLAP and np.array_equal(got0, want0), \
+            "bench sanity check failed: intersect output != planted overlap"
+
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         log("[bench] cpu_baseline (oracle, OpenMP)...")
         cpu = cpu_baseline(us_np, vs_np, args.cpu_seconds)
 

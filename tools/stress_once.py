@@ -3,13 +3,14 @@
 1. 64-way MergeSorted over duplicate-heavy 2M lists, bit-exact vs oracle.
 2. 1024-pair (32 GB) prepared-batch intersect — robustness at scale
    (bounded allocation, planted-overlap check per pair sample)."""
+import os
 import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dgraph_amd import algo, synth  # noqa: E402
 from oracle import bind as orc  # noqa: E402
 
