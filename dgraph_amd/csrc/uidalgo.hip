@@ -2348,6 +2348,157 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact(
     }
 }
 
+/* ==================== kernel: fused per-pair tail ==================== */
+
+/* Replaces k_scan1 + k_scan2 + k_compact + k_compact_small + k_pair_out for
+ * the staged intersect/difference pipeline on the merge-tile layout.
+ * Outputs are per-pair buffers, so a tile only needs its offset WITHIN its
+ * pair: no batch-wide prefix is built.  A workgroup owns one chunk of at
+ * most UA_TAIL_C consecutive tiles of ONE pair (host-built map, chunks never
+ * straddle pairs).  It sums the counts of the pair's earlier tiles (coalesced
+ * L2-hot re-read, Tp^2/(2C) u32 per pair — bounded by the host's per-pair
+ * chunk limit), scans its own counts in LDS and copies.  No workgroup reads
+ * anything another workgroup of this kernel writes: no atomics, fences or
+ * flags.
+ *
+ * UA_TAIL_C: any value up to UA_BLOCK keeps one count per thread (a single
+ * d_block_scan, no per-thread loop).  MEASURED on one box (cfg2 headline /
+ * cfg3 zipf difference, ms per batch; old tail 3.69 on difference):
+ *   C=256  279k pairs/s  3.88     C=32  277k  3.62
+ *   C=64   279k          3.65     C=16  273k  3.59
+ * The sparse headline does not care until the grid gets large (C=16), but a
+ * dense chunk is a 2*C*stride*8-byte copy by ONE workgroup: at C=256 the
+ * whole grid is resident at once (6 workgroups per CU on cfg3) and the
+ * slowest CU sets the time, 5% behind the old 16-tile compactor.  C=64 is
+ * the largest chunk that is not slower than it.  See profiles/tail_fused.md. */
+#ifndef UA_TAIL_C
+#define UA_TAIL_C 64
+#endif
+#ifndef UA_TAIL_MLP
+#define UA_TAIL_MLP 8 /* dense copy: independent loads in flight per lane
+                       * (cfg3 difference at C=128: 3.75 ms vs 3.84 at 4) */
+#endif
+#define UA_TAIL_MAX_TILES 16384 /* per-pair tile cap of the fused tail, see
+                                 * tail_chunk_limit() */
+static_assert(UA_TAIL_C >= 1 && UA_TAIL_C <= UA_BLOCK, "one count per thread");
+
+struct alignas(16) UaTChunk {
+    u64 t0;     /* global index of the chunk's first tile */
+    u32 pair;   /* owning pair */
+    u32 lfirst; /* tiles of this pair before the chunk */
+};
+/* the map holds n_chunks + 1 entries: the sentinel {total_tiles, ~0u, 0}
+ * lets a chunk read its tile count (tiles are globally contiguous) and
+ * whether it is its pair's last from the next entry. */
+
+__global__ __launch_bounds__(UA_BLOCK) void k_tail_fused(
+    const UaDesc *__restrict__ descs, const UaTChunk *__restrict__ cmap,
+    const u32 *__restrict__ tile_cnt, const u64 *__restrict__ staging,
+    u64 stage_stride, const u64 *__restrict__ prim, u64 *__restrict__ pout, int op) {
+    __shared__ u32 s_ex[UA_BLOCK + 1]; /* exclusive scan of the chunk's counts */
+    __shared__ u32 s_ws[UA_BLOCK / 64];
+    __shared__ u64 s_pre[UA_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const UaTChunk ck = cmap[blockIdx.x];
+    const UaTChunk nx = cmap[blockIdx.x + 1];
+    const u32 nt = (u32)(nx.t0 - ck.t0); /* 1..UA_TAIL_C */
+    const UaDesc d = descs[ck.pair];
+    /* the producer clamps tile_cnt to the stride; re-clamp so a corrupt
+     * count can never index past a staging row */
+    const u32 strd = (u32)stage_stride;
+    u32 mine = 0;
+    if ((u32)tid < nt) {
+        mine = tile_cnt[ck.t0 + tid];
+        if (mine > strd) mine = strd;
+    }
+    /* chunk base: counts of the pair's earlier tiles */
+    const u32 *pc = tile_cnt + (ck.t0 - ck.lfirst);
+    u64 pre = 0;
+    for (u32 i = tid; i < ck.lfirst; i += 4 * UA_BLOCK) {
+        u32 x[4]; /* 4 independent L2 loads per round trip */
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            u32 j = i + q * UA_BLOCK;
+            x[q] = j < ck.lfirst ? pc[j] : 0;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) pre += x[q] < strd ? x[q] : strd;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) pre += __shfl_xor(pre, o);
+    if (lane == 0) s_pre[wv] = pre;
+    u32 excl, total;
+    d_block_scan<UA_BLOCK>(tid, mine, s_ws, excl, total); /* barrier inside */
+    s_ex[tid] = excl;
+    if (tid == 0) s_ex[UA_BLOCK] = total; /* s_ex[nt] == total for any nt */
+    u64 base = 0;
+#pragma unroll
+    for (int w = 0; w < UA_BLOCK / 64; w++) base += s_pre[w];
+    __syncthreads();
+    /* per-pair capacity clamp, as k_compact: an element at pair offset g is
+     * written iff g < cap (invalid duplicate/unsorted inputs stay
+     * memory-safe) */
+    const u64 cap = (op == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
+                    : (op == OP_DIFF)    ? d.n
+                                         : (d.n + d.m);
+    if (tid == 0 && nx.pair != ck.pair) {
+        /* pair's last chunk publishes the length, CLAMPED to cap; the old
+         * k_pair_out publishes the unclamped sum.  They agree on valid
+         * inputs, and the clamped value is the number of elements written. */
+        u64 len = base + total;
+        pout[ck.pair] = len < cap ? len : cap;
+    }
+    if (base >= cap || total == 0) return;
+    const u64 room = cap - base;
+    u64 *__restrict__ dst = d.out + base;
+    /* Copy-mode switch at a mean of one wave row (64) per tile.  Below it a
+     * wave-per-tile copy leaves most lanes idle and pays a load->store round
+     * trip per tile, so copy output-indexed (log2 C LDS probes per element buy
+     * fully coalesced stores); at or above it every wave iteration is at
+     * least half full without any search. */
+    if (total < 64u * nt) {
+        const u32 lim = (u64)total < room ? total : (u32)room;
+        for (u32 e = tid; e < lim; e += UA_BLOCK) {
+            /* largest j in [0, nt) with s_ex[j] <= e (skips empty tiles) */
+            u32 lo = 0, hi = nt;
+            while (hi - lo > 1) {
+                u32 mid = (lo + hi) >> 1;
+                if (s_ex[mid] <= e) lo = mid;
+                else hi = mid;
+            }
+            u32 cnt = s_ex[lo + 1] - s_ex[lo];
+            u64 t = ck.t0 + lo;
+            /* mirrors the producer's primary-vs-overflow rule (k_tiles) */
+            const u64 *src = (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
+                                                              : staging + t * stage_stride;
+            dst[e] = src[e - s_ex[lo]];
+        }
+    } else {
+        for (u32 j = wv; j < nt; j += UA_BLOCK / 64) {
+            u32 off = s_ex[j];
+            u32 cnt = s_ex[j + 1] - off;
+            if (cnt == 0 || (u64)off >= room) continue;
+            u64 t = ck.t0 + j;
+            const u64 *src = (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
+                                                              : staging + t * stage_stride;
+            if ((u64)cnt > room - off) cnt = (u32)(room - off);
+            u64 *o = dst + off;
+            /* UA_TAIL_MLP independent loads in flight per lane, then the
+             * stores: a wave walks its tiles serially, so the copy is bound
+             * by load->store round trips unless each one carries enough */
+            for (u32 i = lane; i < cnt; i += 64 * UA_TAIL_MLP) {
+                u64 val[UA_TAIL_MLP];
+#pragma unroll
+                for (int q = 0; q < UA_TAIL_MLP; q++)
+                    val[q] = (i + 64 * q < cnt) ? src[i + 64 * q] : 0;
+#pragma unroll
+                for (int q = 0; q < UA_TAIL_MLP; q++)
+                    if (i + 64 * q < cnt) o[i + 64 * q] = val[q];
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(UA_BLOCK) void k_compact_flat(
     u64 *__restrict__ out, const u32 *__restrict__ cnts, const u64 *__restrict__ offs,
     const u64 *__restrict__ partials, const u64 *__restrict__ staging,
@@ -3116,6 +3267,51 @@ static int run_scan(ua_ctx *c, const u32 *cnt_dev, u64 n, u64 *offs_dev) {
     return UA_OK;
 }
 
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+/* ---- fused tail (k_tail_fused): host-side chunk map ---- */
+
+/* UA_FUSED_TAIL=0 keeps the scan/compact/pair_out tail (same-box A/B) */
+static bool fused_tail_enabled() {
+    const char *e = getenv("UA_FUSED_TAIL");
+    return !(e && e[0] == '0');
+}
+
+/* Per-pair chunk limit.  A pair of Tp tiles re-reads Tp^2/(2C) counts (u32)
+ * to rebuild its chunk bases, against Tp*UA_TILE*8 input bytes its tile
+ * kernel streams from HBM: a ratio of Tp/(8192*C).  The cap of
+ * UA_TAIL_MAX_TILES = 16384 tiles (33.5M path elements, 256 chunks) keeps
+ * that at 3% — 8 MB of L2 hits on a 64 KB count array against 268 MB of HBM
+ * stream; a 10Mx10M pair re-reads 3 MB.  n and m can reach 2^31 (2M tiles),
+ * where the quadratic term would rival the tile kernel, so a batch holding a
+ * larger pair keeps the scanned tail.  UA_TAIL_MAX_CHUNKS overrides; it is
+ * read when the decision is taken (batch create / one-shot call). */
+static u64 tail_chunk_limit() {
+    const char *e = getenv("UA_TAIL_MAX_CHUNKS");
+    if (e && e[0]) {
+        long long v = atoll(e);
+        if (v > 0) return (u64)v;
+    }
+    return UA_TAIL_MAX_TILES / UA_TAIL_C;
+}
+
+/* chunk -> (first tile, pair, tiles before) from the per-pair tile bases,
+ * plus the sentinel entry.  false = some pair exceeds the chunk limit (the
+ * caller keeps the scanned tail). */
+static bool build_tail_chunks(const std::vector<u64> &tb, int n_pairs,
+                              std::vector<UaTChunk> &cm) {
+    const u64 limit = tail_chunk_limit();
+    cm.clear();
+    for (int p = 0; p < n_pairs; p++) {
+        u64 tp = tb[p + 1] - tb[p];
+        if ((tp + UA_TAIL_C - 1) / UA_TAIL_C > limit) return false;
+        for (u64 f = 0; f < tp; f += UA_TAIL_C)
+            cm.push_back({tb[p] + f, (u32)p, (u32)f});
+    }
+    cm.push_back({tb[n_pairs], 0xFFFFFFFFu, 0u});
+    return true;
+}
+
 /* ---- the batched set-algebra pipeline ---- */
 static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
                             uint64_t *out_lens, int op) {
@@ -3137,16 +3333,22 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     tb[n_pairs] = total_tiles;
 
     int rc;
-    /* descs and tb share one allocation and one upload */
+    const bool lb = (op == OP_UNION) ? (bool)UA_LOOKBACK_UNION : (bool)UA_LOOKBACK;
+    /* fused tail: staged intersect/diff whose pairs all fit the chunk limit */
+    std::vector<UaTChunk> cmap;
+    const bool fused = !lb && (op == OP_INTERSECT || op == OP_DIFF) &&
+                       fused_tail_enabled() && build_tail_chunks(tb, n_pairs, cmap);
+    /* descs, tb and the tail's chunk map share one allocation and one upload */
     size_t descs_bytes = descs.size() * sizeof(UaDesc);
-    if ((rc = ws_reserve(c, WS_DESC, descs_bytes + tb.size() * sizeof(u64)))) return rc;
+    size_t o_cmap = align16(descs_bytes + tb.size() * sizeof(u64));
+    size_t cmap_bytes = fused ? cmap.size() * sizeof(UaTChunk) : 0;
+    if ((rc = ws_reserve(c, WS_DESC, o_cmap + cmap_bytes))) return rc;
     if ((rc = ws_reserve(c, WS_TPAIR, (total_tiles + 1) * sizeof(u32)))) return rc;
     if ((rc = ws_reserve(c, WS_TA0, (total_tiles + 1) * sizeof(u32)))) return rc;
     if ((rc = ws_reserve(c, WS_TCNT, (total_tiles + 1) * sizeof(u32)))) return rc;
     if ((rc = ws_reserve(c, WS_TOFF, (total_tiles + 1) * sizeof(u64)))) return rc;
     if ((rc = ws_reserve(c, WS_POUT, (size_t)n_pairs * sizeof(u64)))) return rc;
 
-    const bool lb = (op == OP_UNION) ? (bool)UA_LOOKBACK_UNION : (bool)UA_LOOKBACK;
     u64 stage_stride = 0;
     if (!lb) {
         if (op == OP_INTERSECT) stage_stride = UA_TILE / 2;
@@ -3159,6 +3361,7 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
 
     UaDesc *d_descs = (UaDesc *)c->ws[WS_DESC];
     u64 *d_tb = (u64 *)((u8 *)c->ws[WS_DESC] + descs_bytes);
+    const UaTChunk *d_cmap = (const UaTChunk *)((u8 *)c->ws[WS_DESC] + o_cmap);
     u32 *d_tpair = (u32 *)c->ws[WS_TPAIR];
     u32 *d_ta0 = (u32 *)c->ws[WS_TA0];
     u32 *d_tcnt = (u32 *)c->ws[WS_TCNT];
@@ -3166,9 +3369,10 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     u64 *d_pout = (u64 *)c->ws[WS_POUT];
     u64 *d_stage = (u64 *)c->ws[WS_STAGE];
 
-    std::vector<u8> hostbuf(descs_bytes + tb.size() * sizeof(u64));
+    std::vector<u8> hostbuf(o_cmap + cmap_bytes);
     memcpy(hostbuf.data(), descs.data(), descs_bytes);
     memcpy(hostbuf.data() + descs_bytes, tb.data(), tb.size() * sizeof(u64));
+    if (fused) memcpy(hostbuf.data() + o_cmap, cmap.data(), cmap_bytes);
     HIP_TRY(hipMemcpyAsync(d_descs, hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
     /* zero sentinel so offs[total_tiles] = total output */
@@ -3247,10 +3451,21 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
             }
             HIP_TRY(hipEventRecord(c->ev[1], c->stream));
 
-            if ((rc = run_scan(c, d_tcnt, total_tiles + 1, d_toff))) return rc;
-            u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
+            u64 *d_part = nullptr;
+            if (!fused) {
+                if ((rc = run_scan(c, d_tcnt, total_tiles + 1, d_toff))) return rc;
+                d_part = (u64 *)c->ws[WS_PARTIAL];
+            }
 
-            if (op == OP_UNION) {
+            if (fused) {
+                /* WS_POUT is reused between calls and zero-tile pairs get no
+                 * chunk: their length must read 0 */
+                HIP_TRY(hipMemsetAsync(d_pout, 0, (size_t)n_pairs * sizeof(u64),
+                                       c->stream));
+                hipLaunchKernelGGL(k_tail_fused, dim3((u32)(cmap.size() - 1)),
+                                   dim3(UA_BLOCK), 0, c->stream, d_descs, d_cmap,
+                                   d_tcnt, d_stage, stage_stride, prim, d_pout, op);
+            } else if (op == OP_UNION) {
                 two_kernels = true;
                 HIP_TRY(hipEventRecord(c->ev[2], c->stream));
                 launch_tiles<OP_UNION, MODE_WRITE>(c, d_descs, d_tpair, d_ta0,
@@ -3269,9 +3484,11 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
                                    d_toff, d_part, d_stage, stage_stride, prim,
                                    total_tiles, op);
             }
-            u64 poutblk = ((u64)n_pairs + UA_BLOCK - 1) / UA_BLOCK;
-            hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0,
-                               c->stream, d_toff, d_part, d_tb, n_pairs, d_pout);
+            if (!fused) {
+                u64 poutblk = ((u64)n_pairs + UA_BLOCK - 1) / UA_BLOCK;
+                hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0,
+                                   c->stream, d_toff, d_part, d_tb, n_pairs, d_pout);
+            }
         }
         HIP_TRY(hipMemcpyAsync(out_lens, d_pout, (size_t)n_pairs * sizeof(u64),
                                hipMemcpyDeviceToHost, c->stream));
@@ -3321,6 +3538,14 @@ struct ua_batch {
     void *mem = nullptr;     /* one allocation for all metadata arrays */
     u64 *d_stage = nullptr;  /* lazy; stride UA_TILE (fits intersect + diff) */
     u64 *d_stage_p = nullptr; /* lazy dense primary staging (UA_STAGE_P/tile) */
+    bool stage_p_tried = false; /* allocated (or failed) once: captured tail
+                                 * graphs freeze prim, so it must never change
+                                 * after the first staged run */
+    /* fused tail (k_tail_fused): chunk map built at create; n_tchunks == 0
+     * means this batch keeps the scanned tail (toggle off, or a pair over
+     * the chunk limit) */
+    UaTChunk *d_cmap = nullptr;
+    u64 n_tchunks = 0;
     /* set-1 buffers for the overlapped run_n (aux tail of step i on the
      * tail stream while step i+1's tile kernel fills the other set) */
     u64 *d_stage1 = nullptr;
@@ -3357,8 +3582,6 @@ struct ua_batch {
     u64 *h_pout = nullptr;
 };
 
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
                                ua_batch **out) {
     std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -3393,9 +3616,15 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     u64 Tmax = T > Ta ? T : Ta;
     u64 ncmax = b->nchunks > b->nchunks_a ? b->nchunks : b->nchunks_a;
 
+    std::vector<UaTChunk> cmap;
+    const bool fused = T > 0 && fused_tail_enabled() &&
+                       build_tail_chunks(tb, n_pairs, cmap);
+    if (!fused) cmap.clear();
+
     size_t o_desc = 0;
     size_t o_tb = align16(o_desc + descs.size() * sizeof(UaDesc));
-    size_t o_toff = align16(o_tb + tb.size() * sizeof(u64));
+    size_t o_cmap = align16(o_tb + tb.size() * sizeof(u64));
+    size_t o_toff = align16(o_cmap + cmap.size() * sizeof(UaTChunk));
     size_t o_part = align16(o_toff + (Tmax + 1) * sizeof(u64));
     size_t o_pout = align16(o_part + (ncmax + 1) * sizeof(u64));
     size_t o_tpair = align16(o_pout + (size_t)std::max(n_pairs, 1) * sizeof(u64));
@@ -3415,6 +3644,8 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     u8 *base = (u8 *)b->mem;
     b->d_descs = (UaDesc *)(base + o_desc);
     b->d_tb = (u64 *)(base + o_tb);
+    b->d_cmap = (UaTChunk *)(base + o_cmap);
+    b->n_tchunks = fused ? cmap.size() - 1 : 0;
     b->d_toff = (u64 *)(base + o_toff);
     b->d_part = (u64 *)(base + o_part);
     b->d_pout = (u64 *)(base + o_pout);
@@ -3426,9 +3657,12 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     b->d_tpair_a = (u32 *)(base + o_tpa);
     b->d_bstart = (u32 *)(base + o_bst);
 
-    std::vector<u8> hostbuf(o_tb + tb.size() * sizeof(u64));
+    /* descs, tb and the chunk map go up in one copy */
+    std::vector<u8> hostbuf(o_cmap + cmap.size() * sizeof(UaTChunk));
     memcpy(hostbuf.data(), descs.data(), descs.size() * sizeof(UaDesc));
     memcpy(hostbuf.data() + o_tb, tb.data(), tb.size() * sizeof(u64));
+    if (!cmap.empty())
+        memcpy(hostbuf.data() + o_cmap, cmap.data(), cmap.size() * sizeof(UaTChunk));
     HIP_TRY(hipMemcpyAsync(b->mem, hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(b->d_tba, tba.data(), tba.size() * sizeof(u64),
@@ -3481,7 +3715,9 @@ extern "C" void ua_batch_destroy(ua_ctx *c, ua_batch *b) {
 
 #ifndef UA_GRAPH
 #define UA_GRAPH 1 /* hipGraph-capture the staged pipeline's AUX TAIL
-                    * (scan/compact/pair_out/D2H -> one replay).  The tile
+                    * (k_tail_fused, or scan/compact/pair_out -> one replay;
+                    * the D2H of the lengths is NOT captured — it is enqueued
+                    * once after the last pass of a run_n).  The tile
                     * kernel stays an eager launch so its HIP-event timing
                     * (bench.py roofline leg) remains live — event-record
                     * nodes inside replayed graphs do not update events on
@@ -3527,9 +3763,9 @@ static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
     u64 T = b->total_tiles;
     u64 *stage = set ? b->d_stage1 : b->d_stage;
     u32 *tcnt = set ? b->d_tcnt1 : b->d_tcnt;
-    const u32 *isin;
-    u32 *isout;
-    batch_isplit(b, &isin, &isout);
+    /* the A-indexed kernel neither reads nor writes the split cache: take its
+     * early return BEFORE batch_isplit flips i0_ready, or a later merge-tile
+     * run would read splits nobody stored */
     if ((kop == OP_INTERSECT || kop == OP_DIFF) && aisect_enabled() &&
         b->total_atiles > 0) {
         u64 Ta = b->total_atiles;
@@ -3547,13 +3783,19 @@ static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
         if (record_events) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
         return UA_OK;
     }
+    const u32 *isin;
+    u32 *isout;
+    batch_isplit(b, &isin, &isout);
     if (record_events) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* dense primary staging rides the (otherwise unused) offs arg of the
      * STAGE launch; only for the default kernel and set 0 (overlap keeps
-     * the overflow-only layout, and the experimental kernels ignore it) */
+     * the overflow-only layout, and the experimental kernels ignore it).
+     * One allocation attempt per batch: a failure is recorded, not retried,
+     * so prim is the same on every run and in every captured tail. */
     const u64 *prim = nullptr;
     if (set == 0 && !pp_enabled() && !rp_enabled() && kop != OP_UNION) {
-        if (!b->d_stage_p) {
+        if (!b->stage_p_tried) {
+            b->stage_p_tried = true;
             size_t pbytes = (size_t)(T ? T : 1) * UA_STAGE_P * sizeof(u64);
             if (hipMalloc((void **)&b->d_stage_p, pbytes) != hipSuccess) {
                 b->d_stage_p = nullptr;
@@ -3579,15 +3821,28 @@ static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
     return UA_OK;
 }
 
-/* the aux tail: scan + write/compact + pair_out + D2H of lens (captured
- * into a hipGraph for intersect/diff; union's WRITE pass is a second tile
- * kernel that needs live events, so union stays eager throughout) */
+/* the aux tail, leaving the pair lengths in d_pout (the caller copies them
+ * to the host once, after the last pass).  Intersect/diff on the merge-tile
+ * layout: ONE k_tail_fused.  Otherwise scan + write/compact + pair_out.
+ * Captured into a hipGraph for intersect/diff; union's WRITE pass is a
+ * second tile kernel that needs live events, so union stays eager
+ * throughout. */
 static int batch_tail_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
-                          u64 *host_pout, bool record_events, int set,
-                          hipStream_t st) {
+                          bool record_events, int set, hipStream_t st) {
     /* active tile layout: the A-indexed one when the wave-register
      * intersect produced the counts (intersect/diff with UA_AISECT) */
     bool aA = (kop != OP_UNION) && aisect_enabled() && b->total_atiles > 0;
+    if (kop != OP_UNION && !aA && b->n_tchunks > 0) {
+        /* set 1 (overlap) has no primary region: prim == nullptr */
+        const u64 *prim = (set == 0 && !pp_enabled() && !rp_enabled())
+                              ? b->d_stage_p
+                              : nullptr;
+        hipLaunchKernelGGL(k_tail_fused, dim3((u32)b->n_tchunks), dim3(UA_BLOCK), 0,
+                           st, b->d_descs, b->d_cmap, set ? b->d_tcnt1 : b->d_tcnt,
+                           set ? b->d_stage1 : b->d_stage, stride, prim, b->d_pout,
+                           kop);
+        return UA_OK;
+    }
     u64 T = aA ? b->total_atiles : b->total_tiles;
     u64 nch = aA ? b->nchunks_a : b->nchunks;
     const u32 *tpair = aA ? b->d_tpair_a : b->d_tpair;
@@ -3623,8 +3878,6 @@ static int batch_tail_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
     u64 poutblk = ((u64)b->n_pairs + UA_BLOCK - 1) / UA_BLOCK;
     hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, st,
                        toff, part, tbx, b->n_pairs, b->d_pout);
-    HIP_TRY(hipMemcpyAsync(host_pout, b->d_pout, (size_t)b->n_pairs * sizeof(u64),
-                           hipMemcpyDeviceToHost, st));
     return UA_OK;
 }
 
@@ -3644,7 +3897,7 @@ static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
             hipError_t ce = hipStreamBeginCapture(st,
                                                   hipStreamCaptureModeThreadLocal);
             if (ce == hipSuccess) {
-                int rc = batch_tail_seq(c, b, kop, stride, b->h_pout, false, set, st);
+                int rc = batch_tail_seq(c, b, kop, stride, false, set, st);
                 hipGraph_t gr = nullptr;
                 hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == UA_OK && ee == hipSuccess && gr) {
@@ -3690,7 +3943,7 @@ static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
         }
     }
 #endif
-    return batch_tail_seq(c, b, kop, stride, b->h_pout, record_events, set, st);
+    return batch_tail_seq(c, b, kop, stride, record_events, set, st);
 }
 
 /* n_runs passes of one op over the prepared batch, enqueued back-to-back
@@ -3782,6 +4035,9 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
         const char *ovl_env = getenv("UA_OVERLAP");
         bool ovl = (kop != OP_UNION) && n_runs > 1 && c->stream_tail &&
                    ovl_env && ovl_env[0] == '1';
+        /* the set-1 buffers below are sized for the merge-tile layout
+         * (total_tiles / nchunks); the A-indexed layout can need more */
+        if (aisect_enabled()) ovl = false;
         if (ovl && !b->mem1) {
             size_t o_cnt1 = 0;
             size_t o_off1 = align16(o_cnt1 + (T + 1) * sizeof(u32));
@@ -3818,6 +4074,11 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
                     return rc;
                 HIP_TRY(hipEventRecord(c->oev[2 + s], c->stream_tail));
             }
+            /* lengths: one copy after the last pass (only the last pass's
+             * are returned); tails are serialized on the tail stream */
+            HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
+                                   (size_t)b->n_pairs * sizeof(u64),
+                                   hipMemcpyDeviceToHost, c->stream_tail));
             HIP_TRY(hipStreamSynchronize(c->stream_tail));
             HIP_TRY(hipStreamSynchronize(c->stream));
         } else {
@@ -3827,6 +4088,9 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
                 if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, 0, c->stream)))
                     return rc;
             }
+            HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
+                                   (size_t)b->n_pairs * sizeof(u64),
+                                   hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
         HIP_TRY(hipGetLastError());
