@@ -33,7 +33,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/uidalgo.h"
@@ -59,20 +58,7 @@ typedef uint8_t u8;
                            * which measured better than every software pipeline */
 #endif
 #define UA_WPT (UA_TILE / UA_TBLOCK) /* path elements per thread */
-#ifndef UA_PAD32
-#define UA_PAD32 0 /* 1 = skewed LDS layout (+1 u64 pad per 32): kills the
-                    * 4-way ds_read_b64 bank conflicts of the walk/search
-                    * gathers at power-of-2 lane strides (SQ: conflicts were
-                    * 51% of LDS cycles); fill switches to 4B-lane LDS-DMA
-                    * on 32-element chunks */
-#endif
-#if UA_PAD32
-#define UA_PX(x) ((x) + ((x) >> 5)) /* flat logical u64 index -> physical */
-#define UA_SMEMN (UA_TILE + UA_TILE / 32 + 8)
-#else
-#define UA_PX(x) (x)
-#define UA_SMEMN (UA_TILE + 4)
-#endif
+#define UA_SMEMN (UA_TILE + 4) /* tile LDS: A|B + parity shifts + B lookahead */
 #define UA_SCAN_CHUNK 2048
 #define UA_STAGE_P 64 /* dense primary staging slots (u64/tile): tiles whose
                        * total emission fits go here (512 B apart -> DRAM
@@ -103,74 +89,16 @@ __device__ __forceinline__ u64 d_lower_bound(const u64 *__restrict__ a, u64 n, u
     return lo;
 }
 
-/* merge-path split: #A consumed after `diag` merge steps, A-priority on ties */
-__device__ __forceinline__ u64 d_merge_path(const u64 *__restrict__ A, u64 n,
-                                            const u64 *__restrict__ B, u64 m, u64 diag) {
-    u64 lo = (diag > m) ? diag - m : 0;
-    u64 hi = diag < n ? diag : n;
-    while (lo < hi) {
-        u64 mid = (lo + hi) >> 1;
-        if (A[mid] <= B[diag - 1 - mid]) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int d_merge_path_lds(const u64 *A, int n, const u64 *B, int m,
-                                                int diag) {
+/* merge-path split of one tile in LDS: #A consumed after `diag` merge steps,
+ * A-priority on ties.  A and B sit at u64 offsets aoff/boff of smem. */
+__device__ __forceinline__ int d_merge_path_tile(const u64 *smem, int aoff, int n,
+                                                 int boff, int m, int diag) {
     int lo = diag > m ? diag - m : 0;
     int hi = diag < n ? diag : n;
     while (lo < hi) {
         int mid = (lo + hi) >> 1;
-        if (A[mid] <= B[diag - 1 - mid]) lo = mid + 1;
+        if (smem[aoff + mid] <= smem[boff + diag - 1 - mid]) lo = mid + 1;
         else hi = mid;
-    }
-    return lo;
-}
-
-#ifndef UA_WALK3
-#define UA_WALK3 1 /* 1 = maskless A-value walk for intersect/diff (no em[] bookkeeping) */
-#endif
-
-#ifndef UA_NARY
-#define UA_NARY 0 /* MEASURED REJECT (0.735 vs 0.710 ms on cfg2): 3 probe
-                   * pairs per round (one lgkm wait) halve the search rounds,
-                   * but the extra probe issue outweighs the latency saved —
-                   * the phase is issue-bound after walk3 */
-#endif
-
-/* merge-path probe through the (possibly padded) tile layout */
-__device__ __forceinline__ int d_merge_path_px(const u64 *smem, int aoff, int n,
-                                               int boff, int m, int diag) {
-    int lo = diag > m ? diag - m : 0;
-    int hi = diag < n ? diag : n;
-#if UA_NARY
-    while (hi - lo > 3) {
-        int q = (hi - lo) >> 2;
-        int m1 = lo + q, m2 = lo + 2 * q, m3 = lo + 3 * q;
-        /* all six gathers issue before one wait */
-        u64 a1 = smem[UA_PX(aoff + m1)], b1 = smem[UA_PX(boff + diag - 1 - m1)];
-        u64 a2 = smem[UA_PX(aoff + m2)], b2 = smem[UA_PX(boff + diag - 1 - m2)];
-        u64 a3 = smem[UA_PX(aoff + m3)], b3 = smem[UA_PX(boff + diag - 1 - m3)];
-        bool p1 = a1 <= b1, p2 = a2 <= b2, p3 = a3 <= b3;
-        lo = p3 ? m3 + 1 : (p2 ? m2 + 1 : (p1 ? m1 + 1 : lo));
-        hi = p1 ? (p2 ? (p3 ? hi : m3) : m2) : m1;
-    }
-#endif
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (smem[UA_PX(aoff + mid)] <= smem[UA_PX(boff + diag - 1 - mid)]) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int d_lower_bound_i(const u64 *a, int n, u64 key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (a[mid] >= key) hi = mid;
-        else lo = mid + 1;
     }
     return lo;
 }
@@ -248,157 +176,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_partition(
 /* ==================== kernel: tile set-algebra ==================== */
 
 enum { OP_INTERSECT = 0, OP_UNION = 1, OP_DIFF = 2, OP_MERGE_ALL = 3 };
-enum { MODE_STAGE = 0, MODE_COUNT = 1, MODE_WRITE = 2, MODE_DIRECT = 3,
-       MODE_LOOKBACK = 4 };
-
-/* ---- decoupled-lookback tile prefix (MODE_LOOKBACK) ----
- * Single-pass pipeline: each tile walks once, publishes its emission count,
- * resolves its pair-local exclusive prefix by looking back over predecessor
- * tiles (CUB-style: 64 lanes inspect 64 predecessors per round), and writes
- * its emissions at final positions — no staging buffer, no separate scan /
- * compact / pair_out launches, and union needs ONE walk instead of
- * count+write.  Safe on CDNA4: workgroups dispatch first->last
- * (MI355X_MICROARCH.md §dispatch; the same assumption rocPRIM's device scan
- * ships on), and the 8-byte flag word is an untorn agent-scope (sc1)
- * load/store granule, so no fences are needed — the word itself carries the
- * value.
- *
- * Flag word: [63:48] generation (stale-run guard, wraps via memset),
- * [47:46] status (0 invalid / 1 aggregate / 2 pair-local inclusive prefix),
- * [45:0] value. */
-#define UA_LB_GEN_MAX 0xFFFFull
-__device__ __forceinline__ u64 d_lb_word(u64 gen, u64 status, u64 val) {
-    return (gen << 48) | (status << 46) | val;
-}
-
-/* wave0 (tid<64) resolves the pair-local exclusive prefix of tile t */
-__device__ __forceinline__ u64 d_lb_resolve(u64 *lbf, u64 gen, u64 t, u64 base_t,
-                                            int lane) {
-    u64 run = 0;
-    u64 hi = t;
-    for (;;) {
-        long idx = (long)hi - 1 - lane;
-        int st = 2;
-        u64 val = 0;
-        if (idx >= (long)base_t) {
-            u64 w = __hip_atomic_load(&lbf[idx], __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-            while ((w >> 48) != gen || !((w >> 46) & 3)) {
-                __builtin_amdgcn_s_sleep(1);
-                w = __hip_atomic_load(&lbf[idx], __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-            }
-            st = (int)((w >> 46) & 3);
-            val = w & ((1ull << 46) - 1);
-        }
-        u64 pm = __ballot(st == 2);
-        /* nearest PREFIX lane (smallest back distance); lanes past it add
-         * nothing.  pm==0: whole window is aggregates — sum and slide. */
-        u64 contrib;
-        if (pm) {
-            int k = __ffsll((unsigned long long)pm) - 1;
-            contrib = (lane <= k) ? val : 0;
-        } else {
-            contrib = val;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) contrib += __shfl_xor(contrib, o);
-        run += contrib;
-        if (pm) return run;
-        hi -= 64;
-    }
-}
-
-/* One pass over the thread's merge-path segment.  Emissions are recorded in
- * a statically-indexed register array (em[s], flag bit s) so the walk runs
- * ONCE: count + payload together, no re-walk, no scratch spill (guide §5.4
- * rule 20: runtime-indexed local arrays go to scratch; per-step static
- * indices do not). */
-/* UNION dedup: the reference's MergeSorted emits the merged stream with ALL
- * duplicates collapsed (uidlist.go:417: output==last skips), including
- * duplicates WITHIN one list (TestMergeSorted6/9/10).  Rule: emit iff value
- * != previous emitted value == previous merged-stream value.  A thread's
- * initial "previous" is max(last A before it, last B before it), using the
- * staged tile-boundary elements when its segment starts at a range head. */
-__device__ __forceinline__ u64 d_prev_stream(const u64 *As, int i0, u64 a_before,
-                                             bool has_ab, const u64 *Bs, int j0,
-                                             u64 b_before, bool has_bb, bool &has_prev) {
-    u64 pa = (i0 > 0) ? As[i0 - 1] : a_before;
-    bool hpa = (i0 > 0) || has_ab;
-    u64 pb = (j0 > 0) ? Bs[j0 - 1] : b_before;
-    bool hpb = (j0 > 0) || has_bb;
-    has_prev = hpa || hpb;
-    if (!hpa) return pb;
-    if (!hpb) return pa;
-    return pa > pb ? pa : pb;
-}
-
-template <int OP>
-__device__ __forceinline__ int tile_walk(const u64 *As, int alen, const u64 *Bs, int blen,
-                                         u64 a_before, bool has_ab, u64 b_before,
-                                         bool has_bb, bool has_bn,
-                                         int s0, int s1, int i0,
-                                         u64 (&em)[UA_WPT], u32 &flags) {
-    int i = i0, j = s0 - i0;
-    int cnt = 0;
-    flags = 0;
-    int steps = s1 - s0;
-    int blen_ext = blen + (has_bn ? 1 : 0); /* Bs[blen] is the lookahead slot */
-    /* frontier values live in registers: ONE masked LDS reload per step
-     * instead of re-gathering As[i]/Bs[j] every comparison */
-    u64 a = (i < alen) ? As[i] : 0;
-    u64 b = (j < blen_ext) ? Bs[j] : 0;
-    bool has_prev = false;
-    u64 prev_out = 0;
-    if (OP == OP_UNION)
-        prev_out = d_prev_stream(As, i, a_before, has_ab, Bs, j, b_before, has_bb,
-                                 has_prev);
-#pragma unroll
-    for (int s = 0; s < UA_WPT; s++) {
-        if (s >= steps || (i >= alen && j >= blen)) break;
-        bool takeA = (i < alen) && (j >= blen || a <= b);
-        if (takeA) {
-            if (OP == OP_INTERSECT) {
-                bool match = (j < blen_ext) && (a == b);
-                if (match) {
-                    em[s] = a;
-                    flags |= 1u << s;
-                    cnt++;
-                }
-            } else if (OP == OP_DIFF) {
-                bool match = (j < blen_ext) && (a == b);
-                if (!match) {
-                    em[s] = a;
-                    flags |= 1u << s;
-                    cnt++;
-                }
-            } else { /* UNION: emit iff != previous merged-stream value */
-                if (!has_prev || a != prev_out) {
-                    em[s] = a;
-                    flags |= 1u << s;
-                    cnt++;
-                }
-                prev_out = a;
-                has_prev = true;
-            }
-            i++;
-            if (i < alen) a = As[i];
-        } else {
-            if (OP == OP_UNION) {
-                if (!has_prev || b != prev_out) {
-                    em[s] = b;
-                    flags |= 1u << s;
-                    cnt++;
-                }
-                prev_out = b;
-                has_prev = true;
-            }
-            j++;
-            if (j < blen_ext) b = Bs[j];
-        }
-    }
-    return cnt;
-}
+enum { MODE_STAGE = 0, MODE_COUNT = 1, MODE_WRITE = 2, MODE_DIRECT = 3 };
 
 /* block-wide exclusive scan of per-thread counts: wave __shfl scan + one
  * cross-wave combine — 1 barrier instead of Hillis-Steele's 17 */
@@ -426,68 +204,32 @@ __device__ __forceinline__ void d_block_scan(int tid, u32 cnt, u32 *wsum,
     excl = wbase + incl - cnt;
 }
 
-/* Advance j to the first index in [j, bext) with Bs[idx] >= a: gallop then
- * binary — O(log gap) LDS probes, no serial per-element dependence. */
-__device__ __forceinline__ int d_advance(const u64 *Bs, int bext, int j, u64 a) {
-    if (j >= bext || Bs[j] >= a) return j;
-    int st = 1;
-    while (j + st < bext && Bs[j + st] < a) st <<= 1;
-    int lo = j + (st >> 1) + 1; /* Bs[j + st/2] < a */
-    int hi = j + st;
-    if (hi > bext) hi = bext;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (Bs[mid] >= a) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-/* A-indexed tile pass for INTERSECT/DIFF: threads take contiguous A-index
- * chunks (output order = A order since only A elements emit), and find each
- * A element in the tile's B range by monotone galloping search.  ~2x fewer
- * instructions than the merge walk (the kernel is issue-bound), and no
- * per-thread diagonal search. */
-template <int OP>
-__device__ __forceinline__ int tile_search(const u64 *As, int alen, const u64 *Bs,
-                                           int blen, bool has_bn, int tid,
-                                           u64 (&em)[UA_WPT], u32 &flags) {
-    int lo = (int)(((long)tid * alen) / UA_TBLOCK);
-    int hi = (int)(((long)(tid + 1) * alen) / UA_TBLOCK);
-    int bext = blen + (has_bn ? 1 : 0);
-    int cnt = 0;
-    flags = 0;
-    if (lo >= hi) return 0;
-    int j = d_lower_bound_i(Bs, bext, As[lo]);
-#pragma unroll
-    for (int s = 0; s < UA_WPT; s++) {
-        if (lo + s >= hi) break;
-        u64 a = As[lo + s];
-        j = d_advance(Bs, bext, j, a);
-        bool found = (j < bext) && (Bs[j] == a);
-        bool keep = (OP == OP_INTERSECT) ? found : !found;
-        if (keep) {
-            em[s] = a;
-            flags |= 1u << s;
-            cnt++;
-        }
-    }
-    return cnt;
-}
-
-/* Branchless walk: the asm of the if/else walk is ~25% exec-mask control
- * (s_and_saveexec/s_or_b64/s_cbranch per step).  This variant keeps a
- * 2-deep frontier per side in registers and does ONE unconditional LDS
- * gather per step at a selected clamped address — no divergent branches in
- * the loop body.  As and Bs must live in the SAME LDS array (smem) so the
- * refill address can select between them.  aoff/boff are u64-element
- * offsets of As/Bs within smem. */
+/* Branchless walk for union / merge-all, one pass over the thread's
+ * merge-path segment.  An if/else walk is ~25% exec-mask control
+ * (s_and_saveexec/s_or_b64/s_cbranch per step); this one keeps a 2-deep
+ * frontier per side in registers and does ONE unconditional LDS gather per
+ * step at a selected clamped address — no divergent branches in the loop
+ * body.  As and Bs must live in the SAME LDS array (smem) so the refill
+ * address can select between them.  aoff/boff are u64-element offsets of
+ * As/Bs within smem.  Emissions are recorded in a statically-indexed
+ * register array (em[s], flag bit s) so the walk runs ONCE: count + payload
+ * together, no re-walk, no scratch spill (runtime-indexed local arrays go to
+ * scratch; per-step static indices do not).
+ *
+ * UNION dedup: the reference's MergeSorted emits the merged stream with ALL
+ * duplicates collapsed (uidlist.go:417: output==last skips), including
+ * duplicates WITHIN one list (TestMergeSorted6/9/10).  Rule: emit iff value
+ * != previous emitted value == previous merged-stream value.  A thread's
+ * initial "previous" is max(last A before it, last B before it), using the
+ * staged tile-boundary elements when its segment starts at a range head. */
 template <int OP, int W>
 __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int alen,
                                           int boff, int blen, u64 a_before, bool has_ab,
                                           u64 b_before, bool has_bb,
                                           bool has_bn, int s0, int s1, int i0,
                                           u64 (&em)[W], u32 &flags) {
+    static_assert(OP == OP_UNION || OP == OP_MERGE_ALL,
+                  "intersect/difference take tile_walk3x");
     int i = i0, j = s0 - i0;
     int cnt = 0;
     flags = 0;
@@ -496,18 +238,17 @@ __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int ale
     int amax = alen > 0 ? alen - 1 : 0;
     int bmax = blen_ext > 0 ? blen_ext - 1 : 0;
     /* frontier: cur + next per side, clamped loads (garbage guarded by
-     * i/j bound checks in the predicates); all LDS gathers go through
-     * UA_PX (identity unless UA_PAD32) */
-    u64 a = smembase[UA_PX(aoff + (i < alen ? i : amax))];
-    u64 an = smembase[UA_PX(aoff + ((i + 1) < alen ? (i + 1) : amax))];
-    u64 b = smembase[UA_PX(boff + (j < blen_ext ? j : bmax))];
-    u64 bn = smembase[UA_PX(boff + ((j + 1) < blen_ext ? (j + 1) : bmax))];
+     * i/j bound checks in the predicates) */
+    u64 a = smembase[aoff + (i < alen ? i : amax)];
+    u64 an = smembase[aoff + ((i + 1) < alen ? (i + 1) : amax)];
+    u64 b = smembase[boff + (j < blen_ext ? j : bmax)];
+    u64 bn = smembase[boff + ((j + 1) < blen_ext ? (j + 1) : bmax)];
     bool has_prev = false;
     u64 prev_out = 0;
     if (OP == OP_UNION) {
-        u64 pa = (i > 0) ? smembase[UA_PX(aoff + i - 1)] : a_before;
+        u64 pa = (i > 0) ? smembase[aoff + i - 1] : a_before;
         bool hpa = (i > 0) || has_ab;
-        u64 pb = (j > 0) ? smembase[UA_PX(boff + j - 1)] : b_before;
+        u64 pb = (j > 0) ? smembase[boff + j - 1] : b_before;
         bool hpb = (j > 0) || has_bb;
         has_prev = hpa || hpb;
         prev_out = !hpa ? pb : (!hpb ? pa : (pa > pb ? pa : pb));
@@ -518,24 +259,16 @@ __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int ale
         bool inA = i < alen, inB = j < blen;
         if (!inA && !inB) break;
         bool takeA = inA && (!inB || a <= b);
-        bool eq = (a == b) && (j < blen_ext);
+        u64 val = takeA ? a : b;
         bool emit;
-        if (OP == OP_INTERSECT) {
-            emit = takeA && eq;
-            em[s] = a;
-        } else if (OP == OP_DIFF) {
-            emit = takeA && !eq;
-            em[s] = a;
-        } else if (OP == OP_MERGE_ALL) { /* duplicate-keeping merge (sort runs) */
+        if (OP == OP_MERGE_ALL) { /* duplicate-keeping merge (sort runs) */
             emit = true;
-            em[s] = takeA ? a : b;
         } else { /* UNION: emit iff != previous merged-stream value */
-            u64 val = takeA ? a : b;
             emit = !has_prev || val != prev_out;
-            em[s] = val;
             prev_out = val;
             has_prev = true;
         }
+        em[s] = val;
         flags |= ((u32)emit) << s;
         cnt += emit;
         int ni = i + (takeA ? 1 : 0);
@@ -544,7 +277,7 @@ __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int ale
         int ra = (ni + 1) < alen ? (ni + 1) : amax;
         int rb = (nj + 1) < blen_ext ? (nj + 1) : bmax;
         int raddr = takeA ? (aoff + ra) : (boff + rb);
-        u64 r = smembase[UA_PX(raddr)];
+        u64 r = smembase[raddr];
         a = takeA ? an : a;
         b = takeA ? b : bn;
         an = takeA ? r : an;
@@ -556,30 +289,32 @@ __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int ale
 }
 
 /* COUNT-only walk: tile_walk2 minus the em[] value writes — MODE_COUNT
- * needs only the per-thread emission count (union's first pass; walk3
- * already covers intersect/diff counts).  Dedup state is kept so union
+ * needs only the per-thread emission count (union's first pass; intersect
+ * and difference never run a count pass).  Dedup state is kept so union
  * counts match tile_walk2 exactly. */
 template <int OP, int W>
 __device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int alen,
                                            int boff, int blen, u64 a_before,
                                            bool has_ab, u64 b_before, bool has_bb,
                                            bool has_bn, int s0, int s1, int i0) {
+    static_assert(OP == OP_UNION || OP == OP_MERGE_ALL,
+                  "intersect/difference take tile_walk3x");
     int i = i0, j = s0 - i0;
     int cnt = 0;
     int steps = s1 - s0;
     int blen_ext = blen + (has_bn ? 1 : 0);
     int amax = alen > 0 ? alen - 1 : 0;
     int bmax = blen_ext > 0 ? blen_ext - 1 : 0;
-    u64 a = smembase[UA_PX(aoff + (i < alen ? i : amax))];
-    u64 an = smembase[UA_PX(aoff + ((i + 1) < alen ? (i + 1) : amax))];
-    u64 b = smembase[UA_PX(boff + (j < blen_ext ? j : bmax))];
-    u64 bn = smembase[UA_PX(boff + ((j + 1) < blen_ext ? (j + 1) : bmax))];
+    u64 a = smembase[aoff + (i < alen ? i : amax)];
+    u64 an = smembase[aoff + ((i + 1) < alen ? (i + 1) : amax)];
+    u64 b = smembase[boff + (j < blen_ext ? j : bmax)];
+    u64 bn = smembase[boff + ((j + 1) < blen_ext ? (j + 1) : bmax)];
     bool has_prev = false;
     u64 prev_out = 0;
     if (OP == OP_UNION) {
-        u64 pa = (i > 0) ? smembase[UA_PX(aoff + i - 1)] : a_before;
+        u64 pa = (i > 0) ? smembase[aoff + i - 1] : a_before;
         bool hpa = (i > 0) || has_ab;
-        u64 pb = (j > 0) ? smembase[UA_PX(boff + j - 1)] : b_before;
+        u64 pb = (j > 0) ? smembase[boff + j - 1] : b_before;
         bool hpb = (j > 0) || has_bb;
         has_prev = hpa || hpb;
         prev_out = !hpa ? pb : (!hpb ? pa : (pa > pb ? pa : pb));
@@ -590,11 +325,8 @@ __device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int al
         bool inA = i < alen, inB = j < blen;
         if (!inA && !inB) break;
         bool takeA = inA && (!inB || a <= b);
-        bool eq = (a == b) && (j < blen_ext);
         bool emit;
-        if (OP == OP_INTERSECT) emit = takeA && eq;
-        else if (OP == OP_DIFF) emit = takeA && !eq;
-        else if (OP == OP_MERGE_ALL) emit = true;
+        if (OP == OP_MERGE_ALL) emit = true;
         else {
             u64 val = takeA ? a : b;
             emit = !has_prev || val != prev_out;
@@ -607,7 +339,7 @@ __device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int al
         int ra = (ni + 1) < alen ? (ni + 1) : amax;
         int rb = (nj + 1) < blen_ext ? (nj + 1) : bmax;
         int raddr = takeA ? (aoff + ra) : (boff + rb);
-        u64 r = smembase[UA_PX(raddr)];
+        u64 r = smembase[raddr];
         a = takeA ? an : a;
         b = takeA ? b : bn;
         an = takeA ? r : an;
@@ -618,63 +350,17 @@ __device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int al
     return cnt;
 }
 
-/* INTERSECT/DIFF-only walk with NO value array: emissions are always
- * A-values, so instead of maintaining em[W] (whose per-step conditional
- * writes and register shuffling dominate the issue-bound walk loop), track
- * one takeA bitmask and reconstruct the few matched values from LDS after
- * the scan: A-index at step s = i0 + popcount(amask below s).  ~0.04
- * matches/thread on the 1%-overlap headline shape. */
-template <int OP, int W>
-__device__ __forceinline__ int tile_walk3(const u64 *smembase, int aoff, int alen,
-                                          int boff, int blen, bool has_bn,
-                                          int s0, int s1, int i0,
-                                          u32 &flags, u32 &amask) {
-    static_assert(W <= 32, "masks are u32");
-    int i = i0, j = s0 - i0;
-    int cnt = 0;
-    flags = 0;
-    amask = 0;
-    int steps = s1 - s0;
-    int blen_ext = blen + (has_bn ? 1 : 0);
-    int amax = alen > 0 ? alen - 1 : 0;
-    int bmax = blen_ext > 0 ? blen_ext - 1 : 0;
-    u64 a = smembase[UA_PX(aoff + (i < alen ? i : amax))];
-    u64 an = smembase[UA_PX(aoff + ((i + 1) < alen ? (i + 1) : amax))];
-    u64 b = smembase[UA_PX(boff + (j < blen_ext ? j : bmax))];
-    u64 bn = smembase[UA_PX(boff + ((j + 1) < blen_ext ? (j + 1) : bmax))];
-#pragma unroll
-    for (int s = 0; s < W; s++) {
-        if (s >= steps) break;
-        bool inA = i < alen, inB = j < blen;
-        if (!inA && !inB) break;
-        bool takeA = inA && (!inB || a <= b);
-        bool eq = (a == b) && (j < blen_ext);
-        bool emit = (OP == OP_INTERSECT) ? (takeA && eq) : (takeA && !eq);
-        flags |= ((u32)emit) << s;
-        amask |= ((u32)takeA) << s;
-        cnt += emit;
-        int ni = i + (takeA ? 1 : 0);
-        int nj = j + (takeA ? 0 : 1);
-        int ra = (ni + 1) < alen ? (ni + 1) : amax;
-        int rb = (nj + 1) < blen_ext ? (nj + 1) : bmax;
-        int raddr = takeA ? (aoff + ra) : (boff + rb);
-        u64 r = smembase[UA_PX(raddr)];
-        a = takeA ? an : a;
-        b = takeA ? b : bn;
-        an = takeA ? r : an;
-        bn = takeA ? bn : r;
-        i = ni;
-        j = nj;
-    }
-    return cnt;
-}
-
-/* Dual-chain maskless walk (intersect/diff): two independent 4-step
- * gather chains per thread (halved serial LDS latency), walk3's
- * no-em[] bookkeeping.  Viable because the prepared batch caches BOTH
- * splits (i0 at s0, i0b at smid) — round 1 rejected the dual-chain
- * em[] walk precisely because its second diagonal search cost more
- * than the added MLP recovered. */
+/* INTERSECT/DIFF walk with NO value array: emissions are always A-values,
+ * so instead of maintaining em[W] (whose per-step conditional writes and
+ * register shuffling dominate the issue-bound walk loop), track a takeA
+ * bitmask and reconstruct the few matched values from LDS after the scan:
+ * A-index at step s = i0 + popcount(mask below s).  ~0.04 matches/thread on
+ * the 1%-overlap headline shape.
+ * Dual chain: two independent 4-step gather chains per thread (halved serial
+ * LDS latency), one mask each.  Viable because the prepared batch caches
+ * BOTH splits (i0 at s0, i0b at smid) — round 1 rejected a dual-chain em[]
+ * walk precisely because its second diagonal search cost more than the added
+ * MLP recovered. */
 template <int OP, int W>
 __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int alen,
                                            int boff, int blen, bool has_bn,
@@ -688,10 +374,10 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
     int ia = i0a, ja = s0 - i0a;
     int ib = i0b, jb = smid - i0b;
     int stepsA = smid - s0, stepsB = s1 - smid;
-    u64 aA = smembase[UA_PX(aoff + (ia < alen ? ia : amax))];
-    u64 bA = smembase[UA_PX(boff + (ja < blen_ext ? ja : bmax))];
-    u64 aB = smembase[UA_PX(aoff + (ib < alen ? ib : amax))];
-    u64 bB = smembase[UA_PX(boff + (jb < blen_ext ? jb : bmax))];
+    u64 aA = smembase[aoff + (ia < alen ? ia : amax)];
+    u64 bA = smembase[boff + (ja < blen_ext ? ja : bmax)];
+    u64 aB = smembase[aoff + (ib < alen ? ib : amax)];
+    u64 bB = smembase[boff + (jb < blen_ext ? jb : bmax)];
     int cnt = 0;
     flags = 0;
     amA = 0;
@@ -709,7 +395,7 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
             int ni = ia + (takeA ? 1 : 0), nj = ja + (takeA ? 0 : 1);
             int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
                               : (boff + (nj < blen_ext ? nj : bmax));
-            u64 r = smembase[UA_PX(raddr)];
+            u64 r = smembase[raddr];
             aA = takeA ? r : aA;
             bA = takeA ? bA : r;
             ia = ni;
@@ -726,97 +412,6 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
             int ni = ib + (takeA ? 1 : 0), nj = jb + (takeA ? 0 : 1);
             int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
                               : (boff + (nj < blen_ext ? nj : bmax));
-            u64 r = smembase[UA_PX(raddr)];
-            aB = takeA ? r : aB;
-            bB = takeA ? bB : r;
-            ib = ni;
-            jb = nj;
-        }
-    }
-    return cnt;
-}
-
-/* Dual-chain walk (UA_WALK2X): each thread walks TWO independent
- * half-segments (diagonals s0 and s0+W/2) with interleaved steps — two
- * independent LDS-gather dependency chains per thread to close the
- * latency/MLP gap the SQ counters show (waves park 60% while HBM sits at
- * ~51%). */
-template <int OP>
-__device__ __forceinline__ int tile_walk2x(const u64 *smembase, int aoff, int alen,
-                                           int boff, int blen, u64 a_before, bool has_ab,
-                                           u64 b_before, bool has_bb, bool has_bn,
-                                           int s0, int s1, int i0a, int i0b, int smid,
-                                           u64 (&em)[UA_WPT], u32 &flags) {
-    const u64 *As = smembase + aoff;
-    const u64 *Bs = smembase + boff;
-    int blen_ext = blen + (has_bn ? 1 : 0);
-    int amax = alen > 0 ? alen - 1 : 0;
-    int bmax = blen_ext > 0 ? blen_ext - 1 : 0;
-    constexpr int H = UA_WPT / 2;
-
-    int ia = i0a, ja = s0 - i0a;
-    int ib = i0b, jb = smid - i0b;
-    int stepsA = smid - s0, stepsB = s1 - smid;
-    u64 aA = As[ia < alen ? ia : amax], bA = Bs[ja < blen_ext ? ja : bmax];
-    u64 aB = As[ib < alen ? ib : amax], bB = Bs[jb < blen_ext ? jb : bmax];
-    bool hpA = false, hpB = false;
-    u64 poA = 0, poB = 0;
-    if (OP == OP_UNION) {
-        poA = d_prev_stream(As, ia, a_before, has_ab, Bs, ja, b_before, has_bb, hpA);
-        poB = d_prev_stream(As, ib, a_before, has_ab, Bs, jb, b_before, has_bb, hpB);
-    }
-    int cnt = 0;
-    flags = 0;
-#pragma unroll
-    for (int q = 0; q < H; q++) {
-        /* chain A step */
-        if (q < stepsA && (ia < alen || ja < blen)) {
-            bool inA = ia < alen, inB = ja < blen;
-            bool takeA = inA && (!inB || aA <= bA);
-            bool eq = (aA == bA) && (ja < blen_ext);
-            bool emit;
-            u64 val = takeA ? aA : bA;
-            if (OP == OP_INTERSECT) emit = takeA && eq;
-            else if (OP == OP_DIFF) emit = takeA && !eq;
-            else if (OP == OP_MERGE_ALL) emit = true;
-            else {
-                emit = !hpA || val != poA;
-                poA = val;
-                hpA = true;
-            }
-            em[q] = (OP == OP_INTERSECT || OP == OP_DIFF) ? aA : val;
-            flags |= ((u32)emit) << q;
-            cnt += emit;
-            int ni = ia + (takeA ? 1 : 0), nj = ja + (takeA ? 0 : 1);
-            int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
-                              : (boff + (nj < blen_ext ? nj : bmax));
-            u64 r = smembase[raddr];
-            aA = takeA ? r : aA;
-            bA = takeA ? bA : r;
-            ia = ni;
-            ja = nj;
-        }
-        /* chain B step (independent registers: interleaves with A's gather) */
-        if (q < stepsB && (ib < alen || jb < blen)) {
-            bool inA = ib < alen, inB = jb < blen;
-            bool takeA = inA && (!inB || aB <= bB);
-            bool eq = (aB == bB) && (jb < blen_ext);
-            bool emit;
-            u64 val = takeA ? aB : bB;
-            if (OP == OP_INTERSECT) emit = takeA && eq;
-            else if (OP == OP_DIFF) emit = takeA && !eq;
-            else if (OP == OP_MERGE_ALL) emit = true;
-            else {
-                emit = !hpB || val != poB;
-                poB = val;
-                hpB = true;
-            }
-            em[H + q] = (OP == OP_INTERSECT || OP == OP_DIFF) ? aB : val;
-            flags |= ((u32)emit) << (H + q);
-            cnt += emit;
-            int ni = ib + (takeA ? 1 : 0), nj = jb + (takeA ? 0 : 1);
-            int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
-                              : (boff + (nj < blen_ext ? nj : bmax));
             u64 r = smembase[raddr];
             aB = takeA ? r : aB;
             bB = takeA ? bB : r;
@@ -825,28 +420,6 @@ __device__ __forceinline__ int tile_walk2x(const u64 *smembase, int aoff, int al
         }
     }
     return cnt;
-}
-
-/* cooperative global->LDS fill, 16-B vectorized on the aligned body
- * (8-B/lane loads cap ~60% of the dwordx4 HBM rate — guide §2/G13) */
-__device__ __forceinline__ void d_fill_lds(u64 *dst, const u64 *__restrict__ src,
-                                           int len, int tid) {
-    int head = (int)(((uintptr_t)src >> 3) & 1); /* 1 if src ≡ 8 (mod 16) */
-    if (head > len) head = len;
-    if (tid == 0 && head) dst[0] = src[0];
-    int nvec = (len - head) >> 1;
-    const ulonglong2 *vs = (const ulonglong2 *)(src + head);
-    if ((((uintptr_t)(dst + head)) & 15) == 0) {
-        ulonglong2 *vd = (ulonglong2 *)(dst + head);
-        for (int i = tid; i < nvec; i += UA_TBLOCK) vd[i] = vs[i];
-    } else {
-        for (int i = tid; i < nvec; i += UA_TBLOCK) {
-            ulonglong2 x = vs[i];
-            dst[head + 2 * i] = x.x;
-            dst[head + 2 * i + 1] = x.y;
-        }
-    }
-    for (int i = head + 2 * nvec + tid; i < len; i += UA_TBLOCK) dst[i] = src[i];
 }
 
 template <int OP, int MODE>
@@ -864,7 +437,6 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
     __shared__ u64 s_abefore;
     __shared__ u64 s_bbefore;
-    __shared__ u64 s_run; /* MODE_LOOKBACK: pair-local exclusive prefix */
 
     u64 t = blockIdx.x;
     int tid = threadIdx.x;
@@ -889,34 +461,19 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         i0b_cached = (int)(w >> 16);
     }
 
-#ifndef UA_GLDS
-#define UA_GLDS 1 /* global_load_lds (LDS-DMA) fill: +13% vs the 16B reg-staged fill (4.03 vs 3.58 TB/s on cfg2); 0 = reg-staged */
-#endif
-#if UA_PAD32
-#if !UA_GLDS || UA_SEARCH || UA_WALK2X || (defined(UA_WALK2) && UA_WALK2 == 0)
-#error "UA_PAD32 supports only the default glds + walk2 configuration"
-#endif
-    /* padded layout: 4B-lane DMA has no 16B parity constraint */
-    int aoff = 0;
-    int boff = alen;
-#else
-#if UA_GLDS
-    /* LDS bases chosen so each side's 16B-aligned glds body lines up with
-     * its source POINTER parity (glds writes wave-uniform base + lane*16;
-     * list base pointers are not always 16B aligned — merge-tree runs and
-     * sliced outputs sit at odd u64 offsets) */
+    /* The fill is global_load_lds (LDS-DMA): +13% over a 16B register-staged
+     * fill (4.03 vs 3.58 TB/s on cfg2).  LDS bases are chosen so each side's
+     * 16B-aligned glds body lines up with its source POINTER parity (glds
+     * writes wave-uniform base + lane*16; list base pointers are not always
+     * 16B aligned — merge-tree runs and sliced outputs sit at odd u64
+     * offsets) */
     int ashift = (int)((((uintptr_t)(d.u + a0)) >> 3) & 1);
     int bshift = (int)((((uintptr_t)(d.v + b0)) >> 3) & 1);
     u64 *As = smem + ashift;
     int boff_base = ((ashift + alen + 1) & ~1) + bshift;
     u64 *Bs = smem + boff_base;
-#else
-    u64 *As = smem;                          /* 16-B aligned */
-    u64 *Bs = smem + ((alen + 1) & ~1);      /* rounded up to even: 16-B aligned */
-#endif
     int aoff = (int)(As - smem);
     int boff = (int)(Bs - smem);
-#endif
 
     bool has_ab = (a0 > 0);
     bool has_bb = (b0 > 0);
@@ -927,37 +484,6 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     return;
 #endif
 #if UA_ABLATE != 2
-#if UA_PAD32
-    {
-        /* 4B-lane LDS-DMA on 32-element flat-aligned chunks: each chunk's
-         * physical 256B LDS run is contiguous (pads fall between chunks) */
-        int wv4 = tid >> 6, lane = tid & 63;
-        constexpr int NW = UA_TBLOCK / 64;
-        int c1 = alen & ~31; /* aoff == 0 is chunk-aligned */
-        for (int f = wv4 * 32; f < c1; f += NW * 32) {
-            const u32 *srcp = (const u32 *)(d.u + a0 + f) + lane;
-            __builtin_amdgcn_global_load_lds(srcp, (u32 *)&smem[UA_PX(f)], 4, 0, 0);
-        }
-        for (int i = c1 + tid; i < alen; i += UA_TBLOCK)
-            smem[UA_PX(i)] = d.u[a0 + i];
-
-        int bfirst = ((boff + 31) & ~31);          /* first aligned flat chunk */
-        int b_lead = bfirst - boff;
-        if (b_lead > blen) b_lead = blen;
-        int bend = (boff + blen) & ~31;            /* flat end of aligned body */
-        for (int f = bfirst + wv4 * 32; f < bend; f += NW * 32) {
-            const u32 *srcp = (const u32 *)(d.v + b0 + (f - boff)) + lane;
-            __builtin_amdgcn_global_load_lds(srcp, (u32 *)&smem[UA_PX(f)], 4, 0, 0);
-        }
-        for (int i = tid; i < b_lead; i += UA_TBLOCK)
-            smem[UA_PX(boff + i)] = d.v[b0 + i];
-        int btail = bend - boff;
-        if (btail < b_lead) btail = b_lead;
-        for (int i = btail + tid; i < blen; i += UA_TBLOCK)
-            smem[UA_PX(boff + i)] = d.v[b0 + i];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-#elif UA_GLDS
     {
         /* per-wave LDS-DMA fill: 128 u64 per wave-call (64 lanes x 16 B) */
         int wv4 = tid >> 6, lane = tid & 63;
@@ -988,26 +514,19 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
          * vmcnt, and the compiler's barrier wait cannot be relied on here */
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-#else
-    d_fill_lds(As, d.u + a0, alen, tid);
-    d_fill_lds(Bs, d.v + b0, blen, tid);
-#endif
     if (tid == 0) {
         s_abefore = has_ab ? d.u[a0 - 1] : 0;
         if (OP == OP_UNION) s_bbefore = has_bb ? d.v[b0 - 1] : 0;
-        smem[UA_PX(boff + blen)] = has_bn ? d.v[b1] : 0;
+        smem[boff + blen] = has_bn ? d.v[b1] : 0;
     }
 #endif
     __syncthreads();
 
-#ifndef UA_SEARCH
-#define UA_SEARCH 0 /* 1 = A-indexed gallop search for intersect/diff; measured 3.2 vs 3.45 TB/s for the merge walk on cfg2 - kept for skewed-ratio experiments */
-#endif
-#if UA_SEARCH && UA_WALK3
-#error "UA_SEARCH fills em[]; build it with -DUA_WALK3=0"
-#endif
+    /* intersect/difference emit A-values only: maskless walk, values rebuilt
+     * from LDS at write-back; union/merge-all carry them in em[] */
+    constexpr bool A_ONLY = (OP == OP_INTERSECT || OP == OP_DIFF);
 #if UA_ABLATE == 1 /* fill-only: keep the loads live, skip search+walk */
-    u64 ablate_x = smem[UA_PX(aoff + tid)] + smem[UA_PX(boff + (tid & 127))];
+    u64 ablate_x = smem[aoff + tid] + smem[boff + (tid & 127)];
     asm volatile("" ::"v"(ablate_x));
     u64 em[UA_WPT];
     u32 flags = 0;
@@ -1021,94 +540,50 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     u32 amA = 0, amB = 0; /* walk3x: per-chain takeA bits for reconstruction */
     int w_i0 = 0, w_i0b = 0;
     int cnt;
-#ifndef UA_WALK2
-#define UA_WALK2 1 /* 0 = the branchy register-frontier walk */
-#endif
-#if !UA_PAD32
-    if (UA_SEARCH && OP != OP_UNION && OP != OP_MERGE_ALL) {
-        cnt = tile_search<OP>(As, alen, Bs, blen, has_bn, tid, em, flags);
-    } else
-#endif
-    {
-        int tilelen = alen + blen;
-        int s0 = tid * UA_WPT;
-        int s1 = s0 + UA_WPT;
-        if (s0 > tilelen) s0 = tilelen;
-        if (s1 > tilelen) s1 = tilelen;
-        int smid = s0 + UA_WPT / 2;
-        if (smid > tilelen) smid = tilelen;
-        if (smid < s0) smid = s0;
-        if (smid > s1) smid = s1;
-        int i0 = (i0_cached >= 0) ? i0_cached
-                                  : d_merge_path_px(smem, aoff, alen, boff, blen, s0);
-        int i0b = (i0b_cached >= 0)
-                      ? i0b_cached
-                      : d_merge_path_px(smem, aoff, alen, boff, blen, smid);
-        if (isplit_out)
-            isplit_out[t * UA_TBLOCK + tid] = (u32)i0 | ((u32)i0b << 16);
-        u64 a_before = s_abefore;
-        u64 b_before = (OP == OP_UNION) ? s_bbefore : 0;
-#ifndef UA_WALK2X
-#define UA_WALK2X 0 /* 1 = dual-chain walk (2 independent gather chains/thread) */
-#endif
-#if !UA_PAD32
-        if (UA_WALK2X) {
-            int smid = s0 + UA_WPT / 2;
-            if (smid > tilelen) smid = tilelen;
-            if (smid < s0) smid = s0;
-            if (smid > s1) smid = s1;
-            int i0b = d_merge_path_lds(As, alen, Bs, blen, smid);
-            cnt = tile_walk2x<OP>(smem, (int)(As - smem), alen, (int)(Bs - smem), blen,
-                                  a_before, has_ab, b_before, has_bb, has_bn, s0, s1,
-                                  i0, i0b, smid, em, flags);
-        } else if (!UA_WALK2) {
-            cnt = tile_walk<OP>(As, alen, Bs, blen, a_before, has_ab, b_before,
-                                has_bb, has_bn, s0, s1, i0, em, flags);
-        } else
-#endif
-        if (UA_WALK3 && (OP == OP_INTERSECT || OP == OP_DIFF)) {
-#ifndef UA_DUALWALK
-#define UA_DUALWALK 1 /* 0 = single-chain walk3 (A/B toggle) */
-#endif
-#if UA_DUALWALK
-            cnt = tile_walk3x<OP, UA_WPT>(smem, aoff, alen, boff, blen, has_bn,
-                                          s0, smid, s1, i0, i0b, flags, amA, amB);
-            w_i0 = i0;
-            w_i0b = i0b;
-#else
-            u32 amall;
-            cnt = tile_walk3<OP, UA_WPT>(smem, aoff, alen, boff, blen, has_bn,
-                                         s0, s1, i0, flags, amall);
-            /* express the single mask in the dual-reconstruction form:
-             * amB = high half, w_i0b = i0 + takeA count of the low half */
-            constexpr u32 HM = (1u << (UA_WPT / 2)) - 1;
-            amA = amall & HM;
-            amB = amall >> (UA_WPT / 2);
-            w_i0 = i0;
-            w_i0b = i0 + __popc(amA);
-#endif
-        } else if (MODE == MODE_COUNT) {
-            /* count pass needs no values — skip the em[] bookkeeping */
-            cnt = tile_walk2c<OP, UA_WPT>(smem, aoff, alen, boff, blen, a_before,
-                                          has_ab, b_before, has_bb, has_bn, s0, s1,
-                                          i0);
-            flags = 0;
-        } else {
-            cnt = tile_walk2<OP>(smem, aoff, alen, boff, blen,
-                                 a_before, has_ab, b_before, has_bb, has_bn, s0, s1,
-                                 i0, em, flags);
-        }
-        if (MODE == MODE_DIRECT) {
-            /* OP_MERGE_ALL: every path element emits, so the output position
-             * IS the path position — no scan, no staging, no compaction */
-            u64 *dst = d.out + d0 + (u64)s0;
-            int steps = s1 - s0;
+    int tilelen = alen + blen;
+    int s0 = tid * UA_WPT;
+    int s1 = s0 + UA_WPT;
+    if (s0 > tilelen) s0 = tilelen;
+    if (s1 > tilelen) s1 = tilelen;
+    int smid = s0 + UA_WPT / 2;
+    if (smid > tilelen) smid = tilelen;
+    if (smid < s0) smid = s0;
+    if (smid > s1) smid = s1;
+    int i0 = (i0_cached >= 0) ? i0_cached
+                              : d_merge_path_tile(smem, aoff, alen, boff, blen, s0);
+    int i0b = (i0b_cached >= 0)
+                  ? i0b_cached
+                  : d_merge_path_tile(smem, aoff, alen, boff, blen, smid);
+    if (isplit_out)
+        isplit_out[t * UA_TBLOCK + tid] = (u32)i0 | ((u32)i0b << 16);
+    u64 a_before = s_abefore;
+    u64 b_before = (OP == OP_UNION) ? s_bbefore : 0;
+    if constexpr (A_ONLY) {
+        cnt = tile_walk3x<OP, UA_WPT>(smem, aoff, alen, boff, blen, has_bn,
+                                      s0, smid, s1, i0, i0b, flags, amA, amB);
+        w_i0 = i0;
+        w_i0b = i0b;
+    } else if constexpr (MODE == MODE_COUNT) {
+        /* count pass needs no values — skip the em[] bookkeeping */
+        cnt = tile_walk2c<OP, UA_WPT>(smem, aoff, alen, boff, blen, a_before,
+                                      has_ab, b_before, has_bb, has_bn, s0, s1,
+                                      i0);
+        flags = 0;
+    } else {
+        cnt = tile_walk2<OP>(smem, aoff, alen, boff, blen,
+                             a_before, has_ab, b_before, has_bb, has_bn, s0, s1,
+                             i0, em, flags);
+    }
+    if (MODE == MODE_DIRECT) {
+        /* OP_MERGE_ALL: every path element emits, so the output position
+         * IS the path position — no scan, no staging, no compaction */
+        u64 *dst = d.out + d0 + (u64)s0;
+        int steps = s1 - s0;
 #pragma unroll
-            for (int s = 0; s < UA_WPT; s++) {
-                if (s < steps) dst[s] = em[s];
-            }
-            return;
+        for (int s = 0; s < UA_WPT; s++) {
+            if (s < steps) dst[s] = em[s];
         }
+        return;
     }
 #endif
 #if UA_ABLATE == 3 /* fill+walk, skip scan/write-back */
@@ -1122,75 +597,6 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
 
     if (MODE == MODE_COUNT) {
         if (tid == 0) tile_cnt[t] = total;
-        return;
-    }
-    if (MODE == MODE_LOOKBACK) {
-        /* single-pass: staging = flag array, stage_stride = generation,
-         * offs = per-pair output lengths (d_pout).  See d_lb_resolve. */
-        u64 *lbf = staging;
-        u64 gen = stage_stride;
-        u64 *pout = (u64 *)offs;
-        if (tid == 0) {
-            /* first tile's aggregate IS its inclusive prefix — publish
-             * PREFIX directly so successor windows terminate fast */
-            u64 st = (lt == 0) ? 2ull : 1ull;
-            __hip_atomic_store(&lbf[t], d_lb_word(gen, st, total),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (lt == 0) s_run = 0;
-        }
-        if (lt != 0 && tid < 64) {
-            u64 run = d_lb_resolve(lbf, gen, t, d.tile_base, tid);
-            if (tid == 0) {
-                s_run = run;
-                __hip_atomic_store(&lbf[t], d_lb_word(gen, 2ull, run + total),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        __syncthreads();
-        u64 run = s_run;
-        /* out-capacity clamp: on the contract's duplicate-free sorted inputs
-         * emissions never exceed capacity; on invalid inputs results are
-         * unspecified (like the reference's bin variants) but writes stay
-         * in bounds (the reference is memory-safe there, so are we). */
-        u64 cap = (OP == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
-                  : (OP == OP_DIFF) ? d.n
-                                    : (d.n + d.m);
-        u64 gbase = run + (u64)excl;
-        if (cnt > 0 && gbase < cap) {
-            u64 *dst = d.out + gbase;
-            u64 room = cap - gbase;
-            int lim = (int)((room < (u64)cnt) ? room : (u64)cnt);
-            if (UA_WALK3 && (OP == OP_INTERSECT || OP == OP_DIFF)) {
-                /* reconstruct emitted A-values from the per-chain masks */
-                constexpr int H = UA_WPT / 2;
-                u32 f = flags;
-                int k = 0;
-                while (f && k < lim) {
-                    int s = __builtin_ctz(f);
-                    f &= f - 1;
-                    int idx = (s < H)
-                                  ? w_i0 + __popc(amA & ((1u << s) - 1))
-                                  : w_i0b + __popc(amB & ((1u << (s - H)) - 1));
-                    dst[k++] = smem[UA_PX(aoff + idx)];
-                }
-            } else {
-                int k = 0;
-#pragma unroll
-                for (int s = 0; s < UA_WPT; s++) {
-                    if (flags & (1u << s)) {
-                        if (k < lim) dst[k] = em[s];
-                        k++;
-                    }
-                }
-            }
-        }
-        if (tid == 0) {
-            bool lastt = (t + 1 == total_tiles) || (tile_pair[t + 1] != p);
-            if (lastt) {
-                u64 inc = run + total;
-                pout[p] = inc < cap ? inc : cap;
-            }
-        }
         return;
     }
     u64 *dst;
@@ -1215,7 +621,7 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
               (d_off(offs, partials, t) - d_off(offs, partials, d.tile_base)) + excl;
     }
     if (cnt > 0) {
-        if (UA_WALK3 && (OP == OP_INTERSECT || OP == OP_DIFF)) {
+        if (A_ONLY) {
             /* reconstruct emitted A-values from the per-chain masks */
             constexpr int H = UA_WPT / 2;
             u32 f = flags;
@@ -1226,7 +632,7 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
                 int idx = (s < H)
                               ? w_i0 + __popc(amA & ((1u << s) - 1))
                               : w_i0b + __popc(amB & ((1u << (s - H)) - 1));
-                dst[k++] = smem[UA_PX(aoff + idx)];
+                dst[k++] = smem[aoff + idx];
             }
         } else {
             u32 k = 0;
@@ -1239,927 +645,6 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
             }
         }
     }
-}
-
-/* ---- 2-tile software-pipelined variant: one workgroup processes tiles
- * (2w, 2w+1); the global loads for tile 2w+1 are issued into registers
- * before the walk of tile 2w, so HBM latency hides under compute.  Double
- * LDS buffer (2x16.4KB -> 4 WGs/CU).  Toggle: UA_PIPE. ---- */
-
-struct TileMeta {
-    u32 p;
-    u32 a0, b0;
-    int alen, blen;
-    bool valid, has_ab, has_bn;
-    UaDesc d;
-};
-
-__device__ __forceinline__ TileMeta d_tile_meta(const UaDesc *__restrict__ descs,
-                                                const u32 *__restrict__ tile_pair,
-                                                const u32 *__restrict__ tile_a0,
-                                                u64 total_tiles, u64 t) {
-    TileMeta m;
-    m.valid = (t < total_tiles);
-    if (!m.valid) {
-        m.alen = m.blen = 0;
-        m.a0 = m.b0 = 0;
-        m.has_ab = m.has_bn = false;
-        return m;
-    }
-    m.p = tile_pair[t];
-    m.d = descs[m.p];
-    u64 lt = t - m.d.tile_base;
-    u64 path = m.d.n + m.d.m;
-    u64 d0 = lt * UA_TILE;
-    if (d0 > path) d0 = path;
-    u64 d1 = d0 + UA_TILE;
-    if (d1 > path) d1 = path;
-    u32 a1 = (t + 1 < total_tiles && tile_pair[t + 1] == m.p) ? tile_a0[t + 1]
-                                                              : (u32)m.d.n;
-    m.a0 = tile_a0[t];
-    m.b0 = (u32)(d0 - m.a0);
-    u32 b1 = (u32)(d1 - a1);
-    m.alen = (int)(a1 - m.a0);
-    m.blen = (int)(b1 - m.b0);
-    m.has_ab = (m.a0 > 0);
-    m.has_bn = ((u64)b1 < m.d.m);
-    return m;
-}
-
-/* unified A|B element load into registers (one code path, coalesced) */
-#define UA_PIPE_REGS (UA_WPT)
-__device__ __forceinline__ void d_reg_load(const TileMeta &m, int tid,
-                                           u64 (&val)[UA_PIPE_REGS], u64 &abefore,
-                                           u64 &bbefore, u64 &bnext) {
-#pragma unroll
-    for (int k = 0; k < UA_PIPE_REGS; k++) {
-        int e = tid + k * UA_BLOCK;
-        u64 x = 0;
-        if (e < m.alen) x = m.d.u[m.a0 + e];
-        else if (e - m.alen < m.blen) x = m.d.v[m.b0 + (e - m.alen)];
-        val[k] = x;
-    }
-    if (tid == 0) {
-        abefore = m.has_ab ? m.d.u[m.a0 - 1] : 0;
-        bbefore = (m.b0 > 0) ? m.d.v[m.b0 - 1] : 0;
-        bnext = m.has_bn ? m.d.v[m.b0 + m.blen] : 0;
-    }
-}
-
-__device__ __forceinline__ void d_reg_commit(const TileMeta &m, int tid, u64 *smem,
-                                             const u64 (&val)[UA_PIPE_REGS],
-                                             u64 abefore, u64 bbefore, u64 bnext,
-                                             u64 *s_abefore, u64 *s_bbefore) {
-    int boff = (m.alen + 1) & ~1;
-#pragma unroll
-    for (int k = 0; k < UA_PIPE_REGS; k++) {
-        int e = tid + k * UA_BLOCK;
-        if (e < m.alen) smem[e] = val[k];
-        else if (e - m.alen < m.blen) smem[boff + (e - m.alen)] = val[k];
-    }
-    if (tid == 0) {
-        *s_abefore = abefore;
-        *s_bbefore = bbefore;
-        smem[boff + m.blen] = bnext; /* lookahead slot (garbage if !has_bn) */
-    }
-}
-
-template <int OP, int MODE>
-__device__ __forceinline__ void d_tile_body(const TileMeta &m, u64 t, int tid,
-                                            const u64 *smem, u64 a_before, u64 b_before,
-                                            u64 *__restrict__ staging, u64 stage_stride,
-                                            u32 *__restrict__ tile_cnt,
-                                            const u64 *__restrict__ offs,
-                                            const u64 *__restrict__ partials,
-                                            u32 *scanbuf) {
-    int alen = m.alen, blen = m.blen;
-    int boff = (alen + 1) & ~1;
-    int tilelen = alen + blen;
-    int s0 = tid * UA_WPT;
-    int s1 = s0 + UA_WPT;
-    if (s0 > tilelen) s0 = tilelen;
-    if (s1 > tilelen) s1 = tilelen;
-    u64 em[UA_WPT];
-    u32 flags = 0;
-    int cnt = 0;
-    if (m.valid) {
-        int i0 = d_merge_path_lds(smem, alen, smem + boff, blen, s0);
-        cnt = tile_walk2<OP>(smem, 0, alen, boff, blen, a_before, m.has_ab, b_before,
-                             m.b0 > 0, m.has_bn, s0, s1, i0, em, flags);
-    }
-    u32 excl, total;
-    d_block_scan<UA_BLOCK>(tid, (u32)cnt, scanbuf, excl, total);
-    if (!m.valid) return;
-    if (MODE == MODE_COUNT) {
-        if (tid == 0) tile_cnt[t] = total;
-        return;
-    }
-    u64 *dst;
-    if (MODE == MODE_STAGE) {
-        dst = staging + t * stage_stride + excl;
-        if (tid == 0) tile_cnt[t] = total;
-    } else {
-        dst = m.d.out + (d_off(offs, partials, t) - d_off(offs, partials, m.d.tile_base)) +
-              excl;
-    }
-    if (cnt > 0) {
-        int k = 0;
-#pragma unroll
-        for (int s = 0; s < UA_WPT; s++) {
-            if (flags & (1u << s)) dst[k++] = em[s];
-        }
-    }
-}
-
-template <int OP, int MODE>
-__global__ __launch_bounds__(UA_BLOCK) void k_tiles_pipe(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u32 *__restrict__ tile_a0, u64 total_tiles,
-    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
-    const u64 *__restrict__ offs, const u64 *__restrict__ partials) {
-    __shared__ __align__(16) u64 smem[2][UA_TILE + 4];
-    __shared__ u32 scanbuf[2][UA_BLOCK / 64];
-    __shared__ u64 s_abefore[2];
-    __shared__ u64 s_bbefore[2];
-
-    int tid = threadIdx.x;
-    u64 t0 = (u64)blockIdx.x * 2;
-    u64 t1 = t0 + 1;
-    TileMeta m0 = d_tile_meta(descs, tile_pair, tile_a0, total_tiles, t0);
-    TileMeta m1 = d_tile_meta(descs, tile_pair, tile_a0, total_tiles, t1);
-
-    u64 v0[UA_PIPE_REGS], ab0 = 0, bb0 = 0, bn0 = 0;
-    d_reg_load(m0, tid, v0, ab0, bb0, bn0);
-    d_reg_commit(m0, tid, smem[0], v0, ab0, bb0, bn0, &s_abefore[0], &s_bbefore[0]);
-    /* issue tile-1 loads NOW: they stay in flight across the barrier and
-     * the tile-0 walk */
-    u64 v1[UA_PIPE_REGS], ab1 = 0, bb1 = 0, bn1 = 0;
-    if (m1.valid) d_reg_load(m1, tid, v1, ab1, bb1, bn1);
-    __syncthreads();
-
-    d_tile_body<OP, MODE>(m0, t0, tid, smem[0], s_abefore[0], s_bbefore[0], staging,
-                          stage_stride, tile_cnt, offs, partials, scanbuf[0]);
-    if (!m1.valid) return;
-    d_reg_commit(m1, tid, smem[1], v1, ab1, bb1, bn1, &s_abefore[1], &s_bbefore[1]);
-    __syncthreads();
-    d_tile_body<OP, MODE>(m1, t1, tid, smem[1], s_abefore[1], s_bbefore[1], staging,
-                          stage_stride, tile_cnt, offs, partials, scanbuf[1]);
-}
-
-
-/* ---- 2-buffer glds pipeline (UA_PIPE2): persistent workgroups grid-stride
- * over tiles; the NEXT tile's LDS-DMA fill is issued before walking the
- * current one, and drained only at the iteration-end raw barrier — the
- * guide's canonical glds 2-buffer overlap.  Scalar head/tail/boundary loads
- * are ordered BEFORE the glds issue (an ordinary load-result use after a
- * glds makes hipcc drain vmcnt(0) early — guide §5 trap 4b).  LDS 2x16.4KB
- * -> 4 WGs/CU. ---- */
-
-struct P2Fill {
-    int aoff, boff;
-};
-
-__device__ __forceinline__ P2Fill d_p2_issue(const TileMeta &m, u64 *buf, int tid,
-                                             u64 *s_ab, u64 *s_bb, int for_union) {
-    P2Fill f{0, 0};
-    if (!m.valid) return f;
-    int ashift = (int)((((uintptr_t)(m.d.u + m.a0)) >> 3) & 1);
-    int bshift = (int)((((uintptr_t)(m.d.v + m.b0)) >> 3) & 1);
-    f.aoff = ashift;
-    f.boff = ((ashift + m.alen + 1) & ~1) + bshift;
-    int wv4 = tid >> 6, lane = tid & 63;
-    int ahead = ashift < m.alen ? ashift : m.alen;
-    int abody = (m.alen - ahead) & ~127;
-    int bhead = bshift < m.blen ? bshift : m.blen;
-    int bbody = (m.blen - bhead) & ~127;
-    /* scalar pieces FIRST (ordinary loads complete before any glds issues) */
-    for (int i = ahead + abody + tid; i < m.alen; i += UA_BLOCK)
-        buf[f.aoff + i] = m.d.u[m.a0 + i];
-    if (tid < ahead) buf[f.aoff + tid] = m.d.u[m.a0 + tid];
-    for (int i = bhead + bbody + tid; i < m.blen; i += UA_BLOCK)
-        buf[f.boff + i] = m.d.v[m.b0 + i];
-    if (tid < bhead) buf[f.boff + tid] = m.d.v[m.b0 + tid];
-    if (tid == 0) {
-        *s_ab = m.has_ab ? m.d.u[m.a0 - 1] : 0;
-        if (for_union) *s_bb = (m.b0 > 0) ? m.d.v[m.b0 - 1] : 0;
-        buf[f.boff + m.blen] = m.has_bn ? m.d.v[m.b0 + m.blen] : 0;
-    }
-    /* LDS-DMA body LAST */
-    for (int e = wv4 * 128; e < abody; e += 4 * 128)
-        __builtin_amdgcn_global_load_lds((const u32 *)(m.d.u + m.a0 + ahead + e + lane * 2),
-                                         (u32 *)&buf[f.aoff + ahead + e], 16, 0, 0);
-    for (int e = wv4 * 128; e < bbody; e += 4 * 128)
-        __builtin_amdgcn_global_load_lds((const u32 *)(m.d.v + m.b0 + bhead + e + lane * 2),
-                                         (u32 *)&buf[f.boff + bhead + e], 16, 0, 0);
-    return f;
-}
-
-/* block scan with a RAW barrier (no vmcnt drain: a prefetch glds may be in
- * flight during the scan) */
-__device__ __forceinline__ void d_block_scan_raw(int tid, u32 cnt, u32 *wsum,
-                                                 u32 &excl, u32 &total) {
-    int lane = tid & 63, wv = tid >> 6;
-    u32 incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        u32 x = __shfl_up(incl, o);
-        if (lane >= o) incl += x;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    u32 wbase = 0;
-#pragma unroll
-    for (int w = 0; w < UA_BLOCK / 64; w++) {
-        u32 sv = wsum[w];
-        if (w < wv) wbase += sv;
-    }
-    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    excl = wbase + incl - cnt;
-}
-
-template <int OP, int MODE>
-__global__ __launch_bounds__(UA_BLOCK) void k_tiles_p2(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u32 *__restrict__ tile_a0, u64 total_tiles,
-    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
-    const u64 *__restrict__ offs, const u64 *__restrict__ partials) {
-    __shared__ __align__(16) u64 smem[2][UA_TILE + 4];
-    __shared__ u32 wsum[UA_BLOCK / 64];
-    __shared__ u64 s_ab[2], s_bb[2];
-
-    int tid = threadIdx.x;
-    u64 G = gridDim.x;
-    u64 t = blockIdx.x;
-    if (t >= total_tiles) return;
-
-    TileMeta m = d_tile_meta(descs, tile_pair, tile_a0, total_tiles, t);
-    P2Fill f = d_p2_issue(m, smem[0], tid, &s_ab[0], &s_bb[0], OP == OP_UNION);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    int cur = 0;
-    for (; t < total_tiles; t += G, cur ^= 1) {
-        /* issue the NEXT tile's fill into the other buffer; it stays in
-         * flight across this tile's walk */
-        u64 tn = t + G;
-        TileMeta mn;
-        P2Fill fn{0, 0};
-        mn.valid = false;
-        if (tn < total_tiles) {
-            mn = d_tile_meta(descs, tile_pair, tile_a0, total_tiles, tn);
-            fn = d_p2_issue(mn, smem[cur ^ 1], tid, &s_ab[cur ^ 1], &s_bb[cur ^ 1],
-                            OP == OP_UNION);
-        }
-
-        u64 *buf = smem[cur];
-        int alen = m.alen, blen = m.blen;
-        int tilelen = alen + blen;
-        int s0 = tid * UA_WPT;
-        int s1 = s0 + UA_WPT;
-        if (s0 > tilelen) s0 = tilelen;
-        if (s1 > tilelen) s1 = tilelen;
-        int i0 = d_merge_path_lds(buf + f.aoff, alen, buf + f.boff, blen, s0);
-        u64 em[UA_WPT];
-        u32 flags;
-        int cnt = tile_walk2<OP>(buf, f.aoff, alen, f.boff, blen, s_ab[cur], m.has_ab,
-                                 s_bb[cur], m.b0 > 0, m.has_bn, s0, s1, i0, em, flags);
-
-        if (MODE == MODE_DIRECT) {
-            u64 lt = t - m.d.tile_base;
-            u64 d0 = lt * UA_TILE;
-            u64 *dst = m.d.out + d0 + (u64)s0;
-            int steps = s1 - s0;
-#pragma unroll
-            for (int q = 0; q < UA_WPT; q++)
-                if (q < steps) dst[q] = em[q];
-        } else {
-            u32 excl, total;
-            d_block_scan_raw(tid, (u32)cnt, wsum, excl, total);
-            if (MODE == MODE_COUNT) {
-                if (tid == 0) tile_cnt[t] = total;
-            } else {
-                u64 *dst;
-                if (MODE == MODE_STAGE) {
-                    dst = staging + t * stage_stride + excl;
-                    if (tid == 0) tile_cnt[t] = total;
-                } else {
-                    dst = m.d.out +
-                          (d_off(offs, partials, t) - d_off(offs, partials, m.d.tile_base)) +
-                          excl;
-                }
-                if (cnt > 0) {
-                    int k = 0;
-#pragma unroll
-                    for (int q = 0; q < UA_WPT; q++)
-                        if (flags & (1u << q)) dst[k++] = em[q];
-                }
-            }
-        }
-        /* drain the prefetch + publish this iteration's LDS writes */
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        m = mn;
-        f = fn;
-    }
-}
-
-/* ---- register-staged single-buffer pipeline (UA_RPIPE, runtime env) ----
- *
- * The two round-1 pipeline rejects both HALVED residency (double LDS buffer
- * -> 4 WGs/CU); this variant keeps ONE tile-sized LDS buffer and stages the
- * NEXT tile in registers instead: 512-thread persistent workgroups
- * grid-stride over tiles; each iteration ds_writes the staged registers
- * into LDS, immediately issues the 16-B global loads for tile t+G, and only
- * then walks — so the next tile's HBM latency hides under this tile's
- * search+walk, with LDS residency unchanged.  All barriers are RAW
- * (s_waitcnt lgkmcnt only): __syncthreads fences global too and would drain
- * vmcnt, killing the in-flight prefetch (the presumed reason UA_PIPE saw no
- * overlap).  STAGE/COUNT/WRITE/DIRECT only — LOOKBACK spins on global
- * atomics whose vmcnt waits would serialize the prefetch, and its
- * inter-block dependence needs grid <= residency; it keeps k_tiles. */
-
-#define RP_BLOCK 512
-#define RP_WPT (UA_TILE / RP_BLOCK)
-
-/* global-address-space loads: the staged pointers come out of UaDesc (a
- * value loaded from memory), so hipcc emits FLAT loads for them — and on
- * gfx9-family flat ops count on lgkmcnt too, which would make every raw
- * lgkmcnt barrier wait for the in-flight prefetch.  The addrspacecast pins
- * them to global_load_* (vmcnt only). */
-#define UA_AS_GLOBAL __attribute__((address_space(1)))
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u64x2 d_gload16(const u64 *p) {
-    return *(const UA_AS_GLOBAL u64x2 *)(uintptr_t)p;
-}
-__device__ __forceinline__ u64 d_gload8(const u64 *p) {
-    return *(const UA_AS_GLOBAL u64 *)(uintptr_t)p;
-}
-
-/* Issue the global loads for tile m into registers (two 16-B body units +
- * one lane-designated single: 0=a_before 1=b_before 2=b_next 3=a_head
- * 4=b_head 5=a_tail 6=b_tail).  Bodies are the 16-B aligned middles (same
- * parity layout as the glds fill: As = smem+ashift, Bs = smem+boff so LDS
- * commits are 16-B aligned too).  Bare locals, not a struct: hipcc spills a
- * loop-carried struct of vectors to scratch.  The single is ONE
- * address-selected load, not a switch of loads: exec-masked case loads
- * into one register WAW-serialize on vmcnt(0) drains. */
-__device__ __forceinline__ void d_rp_load(const TileMeta &m, int tid, u64x2 &st0,
-                                          u64x2 &st1, u64 &sng, const u64 *safe) {
-    if (!m.valid) return;
-    int ash = (int)((((uintptr_t)(m.d.u + m.a0)) >> 3) & 1);
-    int bsh = (int)((((uintptr_t)(m.d.v + m.b0)) >> 3) & 1);
-    int ah = ash < m.alen ? ash : m.alen;
-    int bh = bsh < m.blen ? bsh : m.blen;
-    int na2 = (m.alen - ah) >> 1, atail = (m.alen - ah) & 1;
-    int nb2 = (m.blen - bh) >> 1, btail = (m.blen - bh) & 1;
-    /* branchless single load per unit: exec-masked per-branch loads into one
-     * register WAW-serialize on vmcnt drains; out-of-range lanes read `safe`
-     * (a broadcast dummy) instead */
-    {
-        int u = tid;
-        const u64 *p = (u < na2)         ? m.d.u + m.a0 + ah + 2 * u
-                       : (u - na2 < nb2) ? m.d.v + m.b0 + bh + 2 * (u - na2)
-                                         : safe;
-        st0 = d_gload16(p);
-    }
-    {
-        int u = tid + RP_BLOCK;
-        const u64 *p = (u < na2)         ? m.d.u + m.a0 + ah + 2 * u
-                       : (u - na2 < nb2) ? m.d.v + m.b0 + bh + 2 * (u - na2)
-                                         : safe;
-        st1 = d_gload16(p);
-    }
-    const u64 *sp = safe;
-    switch (tid) {
-    case 0: if (m.has_ab) sp = m.d.u + m.a0 - 1; break;
-    case 1: if (m.b0 > 0) sp = m.d.v + m.b0 - 1; break;
-    case 2: if (m.has_bn) sp = m.d.v + m.b0 + m.blen; break;
-    case 3: if (ah) sp = m.d.u + m.a0; break;
-    case 4: if (bh) sp = m.d.v + m.b0; break;
-    case 5: if (atail) sp = m.d.u + m.a0 + m.alen - 1; break;
-    case 6: if (btail) sp = m.d.v + m.b0 + m.blen - 1; break;
-    default: break;
-    }
-    /* opaque barrier on sp: keep hipcc from sinking one load per case */
-    asm volatile("" : "+v"(sp));
-    /* raw value; the not-applicable zeroing happens at COMMIT time so no
-     * instruction here consumes the load (a use would emit a vmcnt drain
-     * in front of the walk and kill the whole prefetch) */
-    sng = d_gload8(sp);
-}
-
-/* ds_write the staged tile into LDS (consumes the staged regs: the
- * compiler's counted vmcnt waits land here, not at a barrier). */
-__device__ __forceinline__ void d_rp_commit(const TileMeta &m, int tid, u64 *smem,
-                                            u64x2 st0, u64x2 st1, u64 sng,
-                                            int &aoff, int &boff, u64 *s_ab,
-                                            u64 *s_bb) {
-    int ash = (int)((((uintptr_t)(m.d.u + m.a0)) >> 3) & 1);
-    int bsh = (int)((((uintptr_t)(m.d.v + m.b0)) >> 3) & 1);
-    aoff = ash;
-    boff = ((ash + m.alen + 1) & ~1) + bsh;
-    if (!m.valid) return;
-    int ah = ash < m.alen ? ash : m.alen;
-    int bh = bsh < m.blen ? bsh : m.blen;
-    int na2 = (m.alen - ah) >> 1, atail = (m.alen - ah) & 1;
-    int nb2 = (m.blen - bh) >> 1, btail = (m.blen - bh) & 1;
-    {
-        int u = tid;
-        if (u < na2)
-            *(u64x2 *)&smem[aoff + ah + 2 * u] = st0;
-        else if (u - na2 < nb2)
-            *(u64x2 *)&smem[boff + bh + 2 * (u - na2)] = st0;
-    }
-    {
-        int u = tid + RP_BLOCK;
-        if (u < na2)
-            *(u64x2 *)&smem[aoff + ah + 2 * u] = st1;
-        else if (u - na2 < nb2)
-            *(u64x2 *)&smem[boff + bh + 2 * (u - na2)] = st1;
-    }
-    /* singles: zero the not-applicable cases here (deferred from load) */
-    switch (tid) {
-    case 0: *s_ab = m.has_ab ? sng : 0; break;
-    case 1: *s_bb = (m.b0 > 0) ? sng : 0; break;
-    case 2: smem[boff + m.blen] = m.has_bn ? sng : 0; break; /* lookahead */
-    case 3: if (ah) smem[aoff] = sng; break;
-    case 4: if (bh) smem[boff] = sng; break;
-    case 5: if (atail) smem[aoff + m.alen - 1] = sng; break;
-    case 6: if (btail) smem[boff + m.blen - 1] = sng; break;
-    default: break;
-    }
-}
-
-/* block scan for NB threads with a RAW barrier (no vmcnt drain) */
-template <int NB>
-__device__ __forceinline__ void d_block_scan_rawN(int tid, u32 cnt, u32 *wsum,
-                                                  u32 &excl, u32 &total) {
-    int lane = tid & 63, wv = tid >> 6;
-    u32 incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        u32 x = __shfl_up(incl, o);
-        if (lane >= o) incl += x;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    u32 wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NB / 64; w++) {
-        u32 sv = wsum[w];
-        if (w < wv) wbase += sv;
-        tot += sv;
-    }
-    total = tot;
-    excl = wbase + incl - cnt;
-}
-
-/* d_tile_meta with the pair descriptor cached from the previous
- * (consecutive) tile: descs[p] is a 3-line struct load that would otherwise
- * sit as a serial L2 round trip at every loop head. */
-__device__ __forceinline__ TileMeta d_tile_meta_seq(const UaDesc *__restrict__ descs,
-                                                    const u32 *__restrict__ tile_pair,
-                                                    const u32 *__restrict__ tile_a0,
-                                                    u64 total_tiles, u64 t, u64 tend,
-                                                    const TileMeta &prev) {
-    TileMeta m;
-    m.valid = (t < tend);
-    if (!m.valid) {
-        m.alen = m.blen = 0;
-        m.a0 = m.b0 = 0;
-        m.has_ab = m.has_bn = false;
-        return m;
-    }
-    m.p = tile_pair[t];
-    if (prev.valid && prev.p == m.p) m.d = prev.d;
-    else m.d = descs[m.p];
-    u64 lt = t - m.d.tile_base;
-    u64 path = m.d.n + m.d.m;
-    u64 d0 = lt * UA_TILE;
-    if (d0 > path) d0 = path;
-    u64 d1 = d0 + UA_TILE;
-    if (d1 > path) d1 = path;
-    u32 a1 = (t + 1 < total_tiles && tile_pair[t + 1] == m.p) ? tile_a0[t + 1]
-                                                              : (u32)m.d.n;
-    m.a0 = tile_a0[t];
-    m.b0 = (u32)(d0 - m.a0);
-    u32 b1 = (u32)(d1 - a1);
-    m.alen = (int)(a1 - m.a0);
-    m.blen = (int)(b1 - m.b0);
-    m.has_ab = (m.a0 > 0);
-    m.has_bn = ((u64)b1 < m.d.m);
-    return m;
-}
-
-template <int OP, int MODE>
-__global__ __launch_bounds__(RP_BLOCK, 8) void k_tiles_rp(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u32 *__restrict__ tile_a0, u64 total_tiles,
-    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
-    const u64 *__restrict__ offs, const u64 *__restrict__ partials) {
-    __shared__ __align__(16) u64 smem[UA_TILE + 4];
-    __shared__ u32 wsum[RP_BLOCK / 64];
-    __shared__ u64 s_ab, s_bb;
-
-    int tid = threadIdx.x;
-    /* contiguous chunk per workgroup: consecutive tiles keep the meta words
-     * (tile_pair/tile_a0, u32) L1-hot and the pair descriptor reg-cached */
-    u64 nb = gridDim.x;
-    u64 len = (total_tiles + nb - 1) / nb;
-    u64 t = (u64)blockIdx.x * len;
-    u64 tend = t + len;
-    if (tend > total_tiles) tend = total_tiles;
-    if (t >= tend) return;
-
-    TileMeta mz;
-    mz.valid = false;
-    TileMeta m = d_tile_meta_seq(descs, tile_pair, tile_a0, total_tiles, t, tend, mz);
-    u64x2 st0 = {}, st1 = {};
-    u64 sng = 0;
-    const u64 *safe = (const u64 *)descs;
-    d_rp_load(m, tid, st0, st1, sng, safe);
-
-    for (; t < tend; t++) {
-        TileMeta mn =
-            d_tile_meta_seq(descs, tile_pair, tile_a0, total_tiles, t + 1, tend, m);
-        int aoff, boff;
-        d_rp_commit(m, tid, smem, st0, st1, sng, aoff, boff, &s_ab, &s_bb);
-        /* pin the commit's stores BEFORE the next tile's load issue: left
-         * free, the scheduler moves the singles ds_writes below the next
-         * sng load sharing their register, and the resulting vmcnt(0)
-         * drains stall wave 0 (and through the barrier, the whole WG) on
-         * the prefetch */
-        __builtin_amdgcn_sched_barrier(0);
-        u64x2 nst0 = {}, nst1 = {};
-        u64 nsng = 0;
-        if (mn.valid) d_rp_load(mn, tid, nst0, nst1, nsng, safe); /* in flight across the walk */
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-
-        int alen = m.alen, blen = m.blen;
-        int tilelen = alen + blen;
-        int s0 = tid * RP_WPT;
-        int s1 = s0 + RP_WPT;
-        if (s0 > tilelen) s0 = tilelen;
-        if (s1 > tilelen) s1 = tilelen;
-        u64 em[RP_WPT];
-        u32 flags = 0;
-        int cnt = 0;
-        {
-            const u64 *As = smem + aoff, *Bs = smem + boff;
-            int i0 = d_merge_path_lds(As, alen, Bs, blen, s0);
-            cnt = tile_walk2<OP>(smem, aoff, alen, boff, blen, s_ab, m.has_ab, s_bb,
-                                 m.b0 > 0, m.has_bn, s0, s1, i0, em, flags);
-        }
-        if (MODE == MODE_DIRECT) {
-            u64 lt = t - m.d.tile_base;
-            u64 *dst = m.d.out + lt * UA_TILE + (u64)s0;
-            int steps = s1 - s0;
-#pragma unroll
-            for (int q = 0; q < RP_WPT; q++)
-                if (q < steps) dst[q] = em[q];
-        } else {
-            u32 excl, total;
-            d_block_scan_rawN<RP_BLOCK>(tid, (u32)cnt, wsum, excl, total);
-            if (MODE == MODE_COUNT) {
-                if (tid == 0) tile_cnt[t] = total;
-            } else {
-                u64 *dst;
-                u32 lim = (u32)cnt;
-                if (MODE == MODE_STAGE) {
-                    /* stride clamp: invalid (duplicate/unsorted) inputs may
-                     * over-emit; keep writes in bounds */
-                    u32 c0 = excl < (u32)stage_stride ? (u32)stage_stride - excl : 0;
-                    if (lim > c0) lim = c0;
-                    dst = staging + t * stage_stride + excl;
-                    if (tid == 0)
-                        tile_cnt[t] = total < (u32)stage_stride ? total
-                                                                : (u32)stage_stride;
-                } else { /* MODE_WRITE: consumed only after the walk, so the
-                            d_off loads draining the prefetch costs little */
-                    dst = m.d.out +
-                          (d_off(offs, partials, t) - d_off(offs, partials, m.d.tile_base)) +
-                          excl;
-                }
-                if (cnt > 0) {
-                    u32 k = 0;
-#pragma unroll
-                    for (int q = 0; q < RP_WPT; q++) {
-                        if (flags & (1u << q)) {
-                            if (k < lim) dst[k] = em[q];
-                            k++;
-                        }
-                    }
-                }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier(); /* LDS reads done before the next commit */
-        /* keep the register shift BELOW the walk: its copies consume the
-         * prefetched values, and hoisted above the barrier they would drain
-         * vmcnt before the walk ever starts */
-        __builtin_amdgcn_sched_barrier(0);
-        m = mn;
-        st0 = nst0;
-        st1 = nst1;
-        sng = nsng;
-    }
-}
-
-
-/* ---- double-buffered glds pipeline at FULL occupancy (UA_PP, runtime env;
- * build with -DUA_TILE=1024 so two buffers fit the round-1 LDS budget) ----
- *
- * PIPE2's structure (issue the next tile's LDS-DMA before walking the
- * current, one vmcnt(0) at the swap) was rejected in round 1 at 4-wave WGs
- * = 16 waves/CU.  At UA_TILE=1024 both buffers fit in 16.4 KB, so 8 WGs x
- * 4 waves keep the full 32 waves/CU AND every WG always has a fill in
- * flight.  This attacks the measured convoy loss: fill-only 0.474 ms,
- * walk-only 0.476, but fill+walk 0.652 — the equal-share HBM service
- * synchronizes fill completions across WGs, so whole CUs alternate
- * all-fill / all-walk phases and HBM idles ~27% of the time.
- * STAGE/COUNT/WRITE/DIRECT only (LOOKBACK keeps k_tiles: its resolve spins
- * on global atomics whose waits would drain the in-flight DMA). */
-template <int OP, int MODE>
-__global__ __launch_bounds__(UA_TBLOCK, 8) void k_tiles_pp(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u32 *__restrict__ tile_a0, u64 total_tiles,
-    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
-    const u64 *__restrict__ offs, const u64 *__restrict__ partials,
-    const u32 *__restrict__ isplit_in, u32 *__restrict__ isplit_out) {
-    static_assert(UA_TBLOCK == UA_BLOCK, "d_p2_issue strides are 4-wave");
-    __shared__ __align__(16) u64 smem[2][UA_TILE + 4];
-    __shared__ u32 scanb[UA_TBLOCK / 64];
-    __shared__ u64 s_ab[2], s_bb[2];
-
-    int tid = threadIdx.x;
-    u64 nb = gridDim.x;
-    u64 len = (total_tiles + nb - 1) / nb;
-    u64 t = (u64)blockIdx.x * len;
-    u64 tend = t + len;
-    if (tend > total_tiles) tend = total_tiles;
-    if (t >= tend) return;
-
-    TileMeta mz;
-    mz.valid = false;
-    TileMeta m = d_tile_meta_seq(descs, tile_pair, tile_a0, total_tiles, t, tend, mz);
-    P2Fill f = d_p2_issue(m, smem[0], tid, &s_ab[0], &s_bb[0], OP == OP_UNION);
-    int cur = 0;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    for (; t < tend; t++, cur ^= 1) {
-        TileMeta mn =
-            d_tile_meta_seq(descs, tile_pair, tile_a0, total_tiles, t + 1, tend, m);
-        P2Fill fn{0, 0};
-        if (mn.valid)
-            fn = d_p2_issue(mn, smem[cur ^ 1], tid, &s_ab[cur ^ 1], &s_bb[cur ^ 1],
-                            OP == OP_UNION); /* DMA in flight across the walk */
-
-        const u64 *buf = smem[cur];
-        int alen = m.alen, blen = m.blen;
-        int tilelen = alen + blen;
-        int s0 = tid * UA_WPT;
-        int s1 = s0 + UA_WPT;
-        if (s0 > tilelen) s0 = tilelen;
-        if (s1 > tilelen) s1 = tilelen;
-        u64 em[UA_WPT];
-        u32 flags = 0, amask = 0;
-        int cnt = 0, w_i0 = 0;
-        int i0 = isplit_in ? (int)(isplit_in[t * UA_TBLOCK + tid] & 0xffffu)
-                           : d_merge_path_px(buf, f.aoff, alen, f.boff, blen, s0);
-        (void)isplit_out; /* pp never participates in the cache */
-        if (UA_WALK3 && (OP == OP_INTERSECT || OP == OP_DIFF)) {
-            cnt = tile_walk3<OP, UA_WPT>(buf, f.aoff, alen, f.boff, blen, m.has_bn,
-                                         s0, s1, i0, flags, amask);
-            w_i0 = i0;
-        } else {
-            cnt = tile_walk2<OP>(buf, f.aoff, alen, f.boff, blen, s_ab[cur], m.has_ab,
-                                 s_bb[cur], m.b0 > 0, m.has_bn, s0, s1, i0, em, flags);
-        }
-        if (MODE == MODE_DIRECT) {
-            u64 lt = t - m.d.tile_base;
-            u64 *dst = m.d.out + lt * UA_TILE + (u64)s0;
-            int steps = s1 - s0;
-#pragma unroll
-            for (int q = 0; q < UA_WPT; q++)
-                if (q < steps) dst[q] = em[q];
-        } else {
-            u32 excl, total;
-            d_block_scan_rawN<UA_TBLOCK>(tid, (u32)cnt, scanb, excl, total);
-            if (MODE == MODE_COUNT) {
-                if (tid == 0) tile_cnt[t] = total;
-            } else {
-                u64 *dst;
-                u32 lim = (u32)cnt;
-                if (MODE == MODE_STAGE) {
-                    /* stride clamp as in k_tiles */
-                    u32 c0 = excl < (u32)stage_stride ? (u32)stage_stride - excl : 0;
-                    if (lim > c0) lim = c0;
-                    dst = staging + t * stage_stride + excl;
-                    if (tid == 0)
-                        tile_cnt[t] = total < (u32)stage_stride ? total
-                                                                : (u32)stage_stride;
-                } else { /* MODE_WRITE: post-walk d_off loads may drain the
-                            DMA, but it has already had the walk to land */
-                    dst = m.d.out +
-                          (d_off(offs, partials, t) - d_off(offs, partials, m.d.tile_base)) +
-                          excl;
-                }
-                if (cnt > 0) {
-                    if (UA_WALK3 && (OP == OP_INTERSECT || OP == OP_DIFF)) {
-                        u32 fl = flags;
-                        u32 k = 0;
-                        while (fl && k < lim) {
-                            int s = __builtin_ctz(fl);
-                            fl &= fl - 1;
-                            int idx = w_i0 + __popc(amask & ((1u << s) - 1));
-                            dst[k++] = buf[UA_PX(f.aoff + idx)];
-                        }
-                    } else {
-                        u32 k = 0;
-#pragma unroll
-                        for (int s = 0; s < UA_WPT; s++) {
-                            if (flags & (1u << s)) {
-                                if (k < lim) dst[k] = em[s];
-                                k++;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        /* drain the next tile's DMA (walk covered its latency) + make sure
-         * every wave is done reading this buffer before it is refilled */
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        m = mn;
-        f = fn;
-    }
-}
-
-
-/* ==================== wave-register intersect (UA_AISECT) ====================
- *
- * Intersect/difference WITHOUT the merge-path walk: A is cut into 512-
- * element wave-tiles (A-indexed, so output order is A order and no
- * per-thread diagonal search exists at all); each WAVE streams 64-wide
- * windows of A and B through REGISTERS (coalesced global loads, no LDS,
- * no barriers) and tests membership with a 6-round shuffle binary search
- * over the B window held one element per lane.  Window advance: A consumes
- * elements <= the window's B max (their membership is fully decided), B
- * consumes elements <= the window's A max (they can never match later A,
- * which is strictly larger).  The phase ablations that motivated this:
- * fill-only 0.474 ms, walk-only 0.476, per-block floor 0.045 — the
- * merge-path kernel's compute phase cost as much as the HBM transfer, and
- * nearly all of it was the per-thread LDS search+walk this design deletes.
- * Aux tail (scan/compact/pair_out) is reused as-is over the A-tile layout
- * (stride UA_AT). */
-
-#define UA_AT 512 /* A elements per wave-tile */
-
-/* per A-tile: owning pair + the lower_bound of its first A value in B
- * (computed once at batch create, like the merge-path partition) */
-__global__ __launch_bounds__(UA_BLOCK) void k_apartition(
-    const UaDesc *__restrict__ descs, const u64 *__restrict__ tba, int n_pairs,
-    u64 total_atiles, u32 *__restrict__ tpair_a, u32 *__restrict__ bstart_a) {
-    u64 t = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
-    if (t >= total_atiles) return;
-    int lo = 0, hi = n_pairs - 1;
-    while (lo < hi) {
-        int mid = (lo + hi + 1) >> 1;
-        if (tba[mid] <= t) lo = mid;
-        else hi = mid - 1;
-    }
-    int p = lo;
-    tpair_a[t] = (u32)p;
-    UaDesc d = descs[p];
-    u64 a_base = (t - tba[p]) * UA_AT;
-    u64 key = (a_base < d.n) ? d.u[a_base] : ~0ull;
-    bstart_a[t] = (u32)d_lower_bound(d.v, d.m, key);
-}
-
-/* lower_bound of a within the b values held one per lane (lanes [0, nb)):
- * 6 fixed rounds of varying-lane shuffles (ds_bpermute). */
-__device__ __forceinline__ int d_wave_lb(u64 b_l, int nb, u64 a) {
-    int pos = 0;
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
-        int cand = pos + step;
-        u64 bm = __shfl(b_l, cand - 1);
-        if (cand <= nb && bm < a) pos = cand;
-    }
-    return pos; /* = count of b < a */
-}
-
-template <int OP>
-__global__ __launch_bounds__(UA_BLOCK) void k_aisect(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tpair_a,
-    const u64 *__restrict__ tba, const u32 *__restrict__ bstart_a,
-    u64 total_atiles, u64 *__restrict__ staging, u32 *__restrict__ tile_cnt) {
-    static_assert(OP == OP_INTERSECT || OP == OP_DIFF, "A-indexed ops only");
-    u64 t = (u64)blockIdx.x * (UA_BLOCK / 64) + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    if (t >= total_atiles) return;
-    u32 p = tpair_a[t];
-    UaDesc d = descs[p];
-    u64 a_base = (t - tba[p]) * UA_AT;
-    if (a_base >= d.n) { /* empty-A pair tail */
-        if (lane == 0) tile_cnt[t] = 0;
-        return;
-    }
-    u64 ia = a_base;
-    u64 ia_end = a_base + UA_AT;
-    if (ia_end > d.n) ia_end = d.n;
-    u64 ib = bstart_a[t];
-    u64 m = d.m;
-    u64 *dst = staging + t * UA_AT;
-    u32 running = 0;
-
-    /* 3-deep register FIFO per side: regs xk[lane] = X[clamp(base+64k+lane)]
-     * for k=0..2; the current 64-wide window [w, w+64) satisfies
-     * w - base < 64, so a window value is a 2-shuffle select over x0/x1 and
-     * x2 is PURE PREFETCH (its load latency hides behind ~a window of
-     * compute before a shift consumes it).  Reloading per window put the
-     * dependent load latency on the serial chain — measured 0.92 ms; the
-     * FIFO takes the loads off the chain. */
-    u64 baseA = ia, baseB = ib;
-    u64 a0r = d.u[(baseA + (u64)lane < ia_end) ? baseA + (u64)lane : ia_end - 1];
-    u64 a1r = d.u[(baseA + 64 + (u64)lane < ia_end) ? baseA + 64 + (u64)lane
-                                                    : ia_end - 1];
-    u64 a2r = d.u[(baseA + 128 + (u64)lane < ia_end) ? baseA + 128 + (u64)lane
-                                                     : ia_end - 1];
-    u64 b0r = 0, b1r = 0, b2r = 0;
-    if (m > 0) {
-        b0r = d.v[(baseB + (u64)lane < m) ? baseB + (u64)lane : m - 1];
-        b1r = d.v[(baseB + 64 + (u64)lane < m) ? baseB + 64 + (u64)lane : m - 1];
-        b2r = d.v[(baseB + 128 + (u64)lane < m) ? baseB + 128 + (u64)lane : m - 1];
-    }
-
-    while (ia < ia_end) {
-        int na = (int)((ia_end - ia < 64) ? (ia_end - ia) : 64);
-        int nb = (int)((m - ib < 64) ? (m - ib) : 64);
-        bool valid_a = lane < na;
-        /* materialize the windows: off in [0, 127), never reaches x2 */
-        int offA = (int)(ia - baseA) + lane;
-        u64 aw0 = __shfl(a0r, offA & 63);
-        u64 aw1 = __shfl(a1r, offA & 63);
-        u64 a = (offA < 64) ? aw0 : aw1;
-        bool b_exh = (ib + (u64)nb >= m);
-        bool eq = false;
-        u64 b_hi = 0;
-        int cB = 0;
-        if (nb > 0) {
-            int offB = (int)(ib - baseB) + lane;
-            u64 bw0 = __shfl(b0r, offB & 63);
-            u64 bw1 = __shfl(b1r, offB & 63);
-            u64 b = (offB < 64) ? bw0 : bw1;
-            int pos = d_wave_lb(b, nb, a);
-            /* UNCONDITIONAL shuffle: under a && short-circuit, lanes with
-             * pos >= nb would go inactive, and a bpermute SOURCE lane that
-             * is inactive in the instruction contributes garbage. */
-            int posc = pos < nb ? pos : 0;
-            u64 bv = __shfl(b, posc);
-            eq = (pos < nb) && (bv == a);
-            b_hi = __shfl(b, nb - 1);
-            /* B consumes elements <= this window's A max: later A values
-             * are strictly larger (duplicate-free contract), so those b
-             * can never match again */
-            u64 a_hi = __shfl(a, na - 1);
-            u64 bm = __ballot((lane < nb) && (b <= a_hi));
-            cB = __popcll(bm);
-        }
-        bool consume = valid_a && (b_exh || a <= b_hi);
-        bool emit = (OP == OP_INTERSECT) ? (consume && eq) : (consume && !eq);
-        u64 em = __ballot(emit);
-        if (emit) {
-            int rank = __popcll(em & ((1ull << lane) - 1));
-            dst[running + rank] = a;
-        }
-        running += (u32)__popcll(em);
-        u64 cm = __ballot(consume);
-        int cA = __popcll(cm);
-        if (nb == 0 && cA == 0) break; /* no progress possible */
-        ia += (u64)cA;
-        ib += (u64)cB;
-        if (ia - baseA >= 64) {
-            baseA += 64;
-            a0r = a1r;
-            a1r = a2r;
-            a2r = d.u[(baseA + 128 + (u64)lane < ia_end) ? baseA + 128 + (u64)lane
-                                                         : ia_end - 1];
-        }
-        if (m > 0 && ib - baseB >= 64) {
-            baseB += 64;
-            b0r = b1r;
-            b1r = b2r;
-            b2r = d.v[(baseB + 128 + (u64)lane < m) ? baseB + 128 + (u64)lane
-                                                    : m - 1];
-        }
-    }
-    if (lane == 0) tile_cnt[t] = running;
 }
 
 /* ==================== kernel: bitonic chunk sort (segmented sort stage 1) ====================
@@ -2305,9 +790,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact_small(
 
 __global__ __launch_bounds__(UA_BLOCK) void k_compact(
     const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u64 *__restrict__ tb /* per-pair first tile in the ACTIVE layout:
-                                  == UaDesc.tile_base for merge tiles, tba
-                                  for the A-indexed (k_aisect) layout */,
+    const u64 *__restrict__ tb /* per-pair first tile (== UaDesc.tile_base) */,
     const u32 *__restrict__ tile_cnt, const u64 *__restrict__ offs,
     const u64 *__restrict__ partials, const u64 *__restrict__ staging,
     u64 stage_stride, const u64 *__restrict__ prim, u64 total_tiles, int op) {
@@ -2351,7 +834,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact(
 /* ==================== kernel: fused per-pair tail ==================== */
 
 /* Replaces k_scan1 + k_scan2 + k_compact + k_compact_small + k_pair_out for
- * the staged intersect/difference pipeline on the merge-tile layout.
+ * the staged intersect/difference pipeline.
  * Outputs are per-pair buffers, so a tile only needs its offset WITHIN its
  * pair: no batch-wide prefix is built.  A workgroup owns one chunk of at
  * most UA_TAIL_C consecutive tiles of ONE pair (host-built map, chunks never
@@ -2525,11 +1008,10 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact_flat(
 /* algo.ApplyFilter (uidlist.go:21): in-place mask compaction.  The Go
  * closure f(uid, i) becomes a precomputed per-element byte mask across the
  * C-ABI (callers evaluate predicates upstream, worker/task.go:1403).  One
- * workgroup per 2048-element chunk; per-task output offsets by the same
- * decoupled-lookback protocol as k_tiles (MODE_LOOKBACK).  out == u
- * (in-place, the reference's shape) is safe: every chunk's loads land
- * (vmcnt) before its count is published, and successors only write after
- * all predecessors published. */
+ * workgroup per 2048-element chunk; per-task output offsets by a
+ * decoupled-lookback prefix (below).  out == u (in-place, the reference's
+ * shape) is safe: every chunk's loads land (vmcnt) before its count is
+ * published, and successors only write after all predecessors published. */
 struct alignas(16) UaFDesc {
     const u64 *u;
     u64 n;
@@ -2538,9 +1020,66 @@ struct alignas(16) UaFDesc {
     u64 tile_base;
 };
 
+/* ---- decoupled-lookback chunk prefix ----
+ * Single pass: each chunk publishes its emission count, resolves its
+ * task-local exclusive prefix by looking back over predecessor chunks
+ * (CUB-style: 64 lanes inspect 64 predecessors per round), and writes its
+ * emissions at final positions — no staging buffer, no separate scan /
+ * compact launches.  Safe on CDNA4: workgroups dispatch first->last
+ * (the same assumption rocPRIM's device scan ships on), and the 8-byte flag
+ * word is an untorn agent-scope load/store granule, so no fences are needed —
+ * the word itself carries the value.  (The tile kernel once had this as a
+ * mode too; it doubled the intersect kernel and was removed)
+ *
+ * Flag word: [63:48] generation (stale-run guard, wraps via memset),
+ * [47:46] status (0 invalid / 1 aggregate / 2 task-local inclusive prefix),
+ * [45:0] value. */
+#define UA_LB_GEN_MAX 0xFFFFull
+__device__ __forceinline__ u64 d_lb_word(u64 gen, u64 status, u64 val) {
+    return (gen << 48) | (status << 46) | val;
+}
+
+/* wave0 (tid<64) resolves the task-local exclusive prefix of chunk t */
+__device__ __forceinline__ u64 d_lb_resolve(u64 *look, u64 gen, u64 t, u64 base_t,
+                                            int lane) {
+    u64 run = 0;
+    u64 hi = t;
+    for (;;) {
+        long idx = (long)hi - 1 - lane;
+        int st = 2;
+        u64 val = 0;
+        if (idx >= (long)base_t) {
+            u64 w = __hip_atomic_load(&look[idx], __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+            while ((w >> 48) != gen || !((w >> 46) & 3)) {
+                __builtin_amdgcn_s_sleep(1);
+                w = __hip_atomic_load(&look[idx], __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+            }
+            st = (int)((w >> 46) & 3);
+            val = w & ((1ull << 46) - 1);
+        }
+        u64 pm = __ballot(st == 2);
+        /* nearest PREFIX lane (smallest back distance); lanes past it add
+         * nothing.  pm==0: whole window is aggregates — sum and slide. */
+        u64 contrib;
+        if (pm) {
+            int k = __ffsll((unsigned long long)pm) - 1;
+            contrib = (lane <= k) ? val : 0;
+        } else {
+            contrib = val;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) contrib += __shfl_xor(contrib, o);
+        run += contrib;
+        if (pm) return run;
+        hi -= 64;
+    }
+}
+
 __global__ __launch_bounds__(UA_BLOCK) void k_filter(
     const UaFDesc *__restrict__ descs, const u64 *__restrict__ tb, int n_tasks,
-    u64 total_tiles, u64 *__restrict__ lbf, u64 gen, u64 *__restrict__ pout) {
+    u64 total_tiles, u64 *__restrict__ look, u64 gen, u64 *__restrict__ pout) {
     __shared__ u32 scan[UA_BLOCK / 64];
     __shared__ u64 s_run;
     u64 t = blockIdx.x;
@@ -2581,15 +1120,15 @@ __global__ __launch_bounds__(UA_BLOCK) void k_filter(
     d_block_scan<UA_BLOCK>(tid, (u32)cnt, scan, excl, total);
     if (tid == 0) {
         u64 st = (lt == 0) ? 2ull : 1ull;
-        __hip_atomic_store(&lbf[t], d_lb_word(gen, st, total), __ATOMIC_RELAXED,
+        __hip_atomic_store(&look[t], d_lb_word(gen, st, total), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
         if (lt == 0) s_run = 0;
     }
     if (lt != 0 && tid < 64) {
-        u64 run = d_lb_resolve(lbf, gen, t, d.tile_base, tid);
+        u64 run = d_lb_resolve(look, gen, t, d.tile_base, tid);
         if (tid == 0) {
             s_run = run;
-            __hip_atomic_store(&lbf[t], d_lb_word(gen, 2ull, run + total),
+            __hip_atomic_store(&look[t], d_lb_word(gen, 2ull, run + total),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -2950,19 +1489,6 @@ __global__ __launch_bounds__(UA_BLOCK) void k_copy_len(
         out[i] = src[i];
 }
 
-#ifndef UA_PIPE
-#define UA_PIPE 0 /* 1 = 2-tile software-pipelined tile kernel (A/B toggle) */
-#endif
-#ifndef UA_PIPE2
-#define UA_PIPE2 0 /* 1 = persistent 2-buffer glds pipeline (A/B toggle) */
-#endif
-
-template <int OP, int MODE>
-static void launch_tiles(ua_ctx *c, const UaDesc *descs, const u32 *tpair,
-                         const u32 *ta0, u64 T, u64 *stage, u64 stride, u32 *tcnt,
-                         const u64 *offs, const u64 *part,
-                         const u32 *isin = nullptr, u32 *isout = nullptr);
-
 /* ==================== host shim ==================== */
 
 static thread_local hipError_t g_last_hip = hipSuccess;
@@ -2979,7 +1505,7 @@ static thread_local hipError_t g_last_hip = hipSuccess;
 enum {
     WS_DESC = 0, WS_TB, WS_TPAIR, WS_TA0, WS_TCNT, WS_TOFF, WS_PARTIAL,
     WS_STAGE, WS_STAGEP, WS_POUT, WS_HU, WS_HV, WS_HOUT, WS_PACK, WS_SCRATCH_A,
-    WS_SCRATCH_B, WS_LBF, WS_COUNT
+    WS_SCRATCH_B, WS_LOOK, WS_COUNT
 };
 
 struct ua_ctx {
@@ -2990,9 +1516,9 @@ struct ua_ctx {
     hipEvent_t ev[4] = {};
     hipStream_t stream_tail = nullptr; /* aux-tail overlap (run_n) */
     hipEvent_t oev[4] = {}; /* [0..1]=tile_done per set, [2..3]=tail_done */
-    /* decoupled-lookback flag array (WS_LBF) bookkeeping */
-    uint32_t lbf_gen = 0;
-    size_t lbf_cleared = 0; /* bytes of the CURRENT WS_LBF allocation zeroed */
+    /* ApplyFilter's lookback flag array (WS_LOOK) bookkeeping */
+    uint32_t look_gen = 0;
+    size_t look_cleared = 0; /* bytes of the CURRENT WS_LOOK allocation zeroed */
     uint32_t *d_viol = nullptr; /* pack-limit validation flag (1 u32) */
     /* stats */
     uint64_t n_launches = 0;
@@ -3069,40 +1595,22 @@ static int ws_reserve(ua_ctx *c, int slot, size_t bytes) {
     return UA_OK;
 }
 
-/* Which ops run the single-pass decoupled-lookback pipeline.
- * MEASURED (r02, cfg2 192x1Mx1M): lookback doubles the intersect kernel
- * (0.76 -> 1.47 ms) — a tile cannot write until every same-pair predecessor
- * has finished its walk, so each tile's lifetime spans ~2 walk phases and
- * 8 WGs/CU cannot hide the parked resolve.  For intersect/difference the
- * staged scan+compact pipeline (outputs ~1% of inputs -> staging is free)
- * is strictly better; for UNION the lookback removes a FULL second data
- * pass (count+write -> one walk), which outweighs the same wait.  */
-#ifndef UA_LOOKBACK
-#define UA_LOOKBACK 0 /* intersect/diff: 1 = lookback, 0 = staged (default) */
-#endif
-#ifndef UA_LOOKBACK_UNION
-#define UA_LOOKBACK_UNION 0 /* union/merge-tree single-pass lookback: MEASURED
-                             * WORSE on cfg3 (125 vs 145 G elems/s) — the
-                             * same-pair predecessor wait costs more than the
-                             * saved second read on long tile chains */
-#endif
-
-/* Acquire the ctx-level lookback flag array for T tiles with a fresh
- * generation.  The array must read as "stale" for the new generation:
+/* Acquire the ctx-level lookback flag array (k_filter) for T chunks with a
+ * fresh generation.  The array must read as "stale" for the new generation:
  * guaranteed by zeroing on (re)allocation and re-zeroing when the 16-bit
  * generation wraps. */
-[[maybe_unused]] static int lb_acquire_ws(ua_ctx *c, u64 T, u64 **flags, u64 *gen) {
-    int rc = ws_reserve(c, WS_LBF, (size_t)T * sizeof(u64));
+static int lb_acquire_ws(ua_ctx *c, u64 T, u64 **flags, u64 *gen) {
+    int rc = ws_reserve(c, WS_LOOK, (size_t)T * sizeof(u64));
     if (rc) return rc;
-    u64 *f = (u64 *)c->ws[WS_LBF];
-    if (c->lbf_cleared < c->ws_cap[WS_LBF] || c->lbf_gen >= UA_LB_GEN_MAX) {
-        HIP_TRY(hipMemsetAsync(f, 0, c->ws_cap[WS_LBF], c->stream));
-        c->lbf_cleared = c->ws_cap[WS_LBF];
-        c->lbf_gen = 0;
+    u64 *f = (u64 *)c->ws[WS_LOOK];
+    if (c->look_cleared < c->ws_cap[WS_LOOK] || c->look_gen >= UA_LB_GEN_MAX) {
+        HIP_TRY(hipMemsetAsync(f, 0, c->ws_cap[WS_LOOK], c->stream));
+        c->look_cleared = c->ws_cap[WS_LOOK];
+        c->look_gen = 0;
     }
-    c->lbf_gen += 1;
+    c->look_gen += 1;
     *flags = f;
-    *gen = c->lbf_gen;
+    *gen = c->look_gen;
     return UA_OK;
 }
 
@@ -3158,97 +1666,13 @@ extern "C" int ua_stats_get(ua_ctx *c, uint64_t *n_launches, double *kernel_ms,
     return UA_OK;
 }
 
-/* UA_RPIPE=0 disables the register-staged pipelined tile kernel (see
- * k_tiles_rp); default on for STAGE/COUNT/WRITE/DIRECT. */
-static int pp_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("UA_PP");
-        v = (e && e[0]) ? (e[0] != '0') : 0;
-    }
-    return v;
-}
-
-static int rp_enabled() {
-#if UA_PAD32
-    return 0; /* k_tiles_rp commits an unpadded layout */
-#else
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("UA_RPIPE");
-        v = (e && e[0]) ? (e[0] != '0') : 0;
-    }
-    return v;
-#endif
-}
-
-/* persistent grid for k_tiles_rp: residency blocks (occupancy API x CUs).
- * Oversizing is harmless here (no inter-block deps in these modes). */
-static u32 rp_grid(const void *kfn, u64 T) {
-    static std::mutex mu;
-    static std::unordered_map<const void *, u32> cache;
-    u32 g;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(kfn);
-        if (it != cache.end()) {
-            g = it->second;
-        } else {
-            int nb = 0, ndev = 0, cus = 256;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, RP_BLOCK, 0);
-            if (hipGetDevice(&ndev) == hipSuccess) {
-                hipDeviceProp_t p;
-                if (hipGetDeviceProperties(&p, ndev) == hipSuccess)
-                    cus = p.multiProcessorCount;
-            }
-            if (nb < 1) nb = 1;
-            g = (u32)nb * (u32)cus;
-            cache.emplace(kfn, g);
-        }
-    }
-    return (u64)g < T ? g : (u32)T;
-}
-
-/* ---- flat scan helper: cnt u32[n] (+1 zero sentinel at n-1 position
- * provided by caller) -> offs u64[n] exclusive scan ---- */
+/* one workgroup per tile on the main stream; isin/isout are the prepared
+ * batch's cached merge-path splits (see k_tiles) */
 template <int OP, int MODE>
 static void launch_tiles(ua_ctx *c, const UaDesc *descs, const u32 *tpair,
                          const u32 *ta0, u64 T, u64 *stage, u64 stride, u32 *tcnt,
                          const u64 *offs, const u64 *part,
-                         const u32 *isin, u32 *isout) {
-    if constexpr (MODE != MODE_LOOKBACK) {
-        if (pp_enabled()) {
-            u32 G = rp_grid((const void *)k_tiles_pp<OP, MODE>, T);
-            hipLaunchKernelGGL((k_tiles_pp<OP, MODE>), dim3(G), dim3(UA_TBLOCK), 0,
-                               c->stream, descs, tpair, ta0, T, stage, stride, tcnt,
-                               offs, part, isin, isout);
-            return;
-        }
-        if (rp_enabled()) {
-            u32 G = rp_grid((const void *)k_tiles_rp<OP, MODE>, T);
-            hipLaunchKernelGGL((k_tiles_rp<OP, MODE>), dim3(G), dim3(RP_BLOCK), 0,
-                               c->stream, descs, tpair, ta0, T, stage, stride, tcnt,
-                               offs, part);
-            return;
-        }
-    }
-#if UA_PIPE
-    if constexpr (MODE != MODE_DIRECT && MODE != MODE_LOOKBACK) {
-        hipLaunchKernelGGL((k_tiles_pipe<OP, MODE>), dim3((u32)((T + 1) / 2)),
-                           dim3(UA_BLOCK), 0, c->stream, descs, tpair, ta0, T, stage,
-                           stride, tcnt, offs, part);
-        return;
-    }
-#endif
-#if UA_PIPE2
-    if constexpr (MODE != MODE_LOOKBACK) {
-        u64 G = T < 1024 ? T : 1024; /* 4 WGs/CU x 256 CUs resident */
-        hipLaunchKernelGGL((k_tiles_p2<OP, MODE>), dim3((u32)G), dim3(UA_BLOCK), 0,
-                           c->stream, descs, tpair, ta0, T, stage, stride, tcnt, offs,
-                           part);
-        return;
-    }
-#endif
+                         const u32 *isin = nullptr, u32 *isout = nullptr) {
     hipLaunchKernelGGL((k_tiles<OP, MODE>), dim3((u32)T), dim3(UA_TBLOCK), 0, c->stream,
                        descs, tpair, ta0, T, stage, stride, tcnt, offs, part,
                        isin, isout);
@@ -3333,10 +1757,9 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     tb[n_pairs] = total_tiles;
 
     int rc;
-    const bool lb = (op == OP_UNION) ? (bool)UA_LOOKBACK_UNION : (bool)UA_LOOKBACK;
     /* fused tail: staged intersect/diff whose pairs all fit the chunk limit */
     std::vector<UaTChunk> cmap;
-    const bool fused = !lb && (op == OP_INTERSECT || op == OP_DIFF) &&
+    const bool fused = (op == OP_INTERSECT || op == OP_DIFF) &&
                        fused_tail_enabled() && build_tail_chunks(tb, n_pairs, cmap);
     /* descs, tb and the tail's chunk map share one allocation and one upload */
     size_t descs_bytes = descs.size() * sizeof(UaDesc);
@@ -3350,13 +1773,11 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     if ((rc = ws_reserve(c, WS_POUT, (size_t)n_pairs * sizeof(u64)))) return rc;
 
     u64 stage_stride = 0;
-    if (!lb) {
-        if (op == OP_INTERSECT) stage_stride = UA_TILE / 2;
-        else if (op == OP_DIFF) stage_stride = UA_TILE;
-        if (stage_stride) {
-            if ((rc = ws_reserve(c, WS_STAGE, total_tiles * stage_stride * sizeof(u64)))) return rc;
-            if ((rc = ws_reserve(c, WS_STAGEP, total_tiles * UA_STAGE_P * sizeof(u64)))) return rc;
-        }
+    if (op == OP_INTERSECT) stage_stride = UA_TILE / 2;
+    else if (op == OP_DIFF) stage_stride = UA_TILE;
+    if (stage_stride) {
+        if ((rc = ws_reserve(c, WS_STAGE, total_tiles * stage_stride * sizeof(u64)))) return rc;
+        if ((rc = ws_reserve(c, WS_STAGEP, total_tiles * UA_STAGE_P * sizeof(u64)))) return rc;
     }
 
     UaDesc *d_descs = (UaDesc *)c->ws[WS_DESC];
@@ -3411,94 +1832,66 @@ static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
         }
 
         bool two_kernels = false;
-        if (lb) {
-            u64 *d_lbf;
-            u64 gen;
-            if ((rc = lb_acquire_ws(c, total_tiles, &d_lbf, &gen))) return rc;
-            HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-            if (op == OP_INTERSECT) {
-                launch_tiles<OP_INTERSECT, MODE_LOOKBACK>(c, d_descs, d_tpair, d_ta0,
-                                                          total_tiles, d_lbf, gen,
-                                                          nullptr, d_pout, nullptr);
-            } else if (op == OP_DIFF) {
-                launch_tiles<OP_DIFF, MODE_LOOKBACK>(c, d_descs, d_tpair, d_ta0,
-                                                     total_tiles, d_lbf, gen, nullptr,
-                                                     d_pout, nullptr);
-            } else {
-                launch_tiles<OP_UNION, MODE_LOOKBACK>(c, d_descs, d_tpair, d_ta0,
-                                                      total_tiles, d_lbf, gen, nullptr,
-                                                      d_pout, nullptr);
-            }
-            HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+        const u64 *prim = (op != OP_UNION) ? (const u64 *)c->ws[WS_STAGEP] : nullptr;
+        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+        if (op == OP_INTERSECT) {
+            launch_tiles<OP_INTERSECT, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
+                                                   total_tiles, d_stage,
+                                                   stage_stride, d_tcnt, prim,
+                                                   nullptr);
+        } else if (op == OP_DIFF) {
+            launch_tiles<OP_DIFF, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
+                                              total_tiles, d_stage, stage_stride,
+                                              d_tcnt, prim, nullptr);
         } else {
-            const u64 *prim = (!pp_enabled() && !rp_enabled() && op != OP_UNION)
-                                  ? (const u64 *)c->ws[WS_STAGEP]
-                                  : nullptr;
-            HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-            if (op == OP_INTERSECT) {
-                launch_tiles<OP_INTERSECT, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
-                                                       total_tiles, d_stage,
-                                                       stage_stride, d_tcnt, prim,
-                                                       nullptr);
-            } else if (op == OP_DIFF) {
-                launch_tiles<OP_DIFF, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
-                                                  total_tiles, d_stage, stage_stride,
-                                                  d_tcnt, prim, nullptr);
-            } else {
-                launch_tiles<OP_UNION, MODE_COUNT>(c, d_descs, d_tpair, d_ta0,
-                                                   total_tiles, nullptr, 0, d_tcnt,
-                                                   nullptr, nullptr);
-            }
-            HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+            launch_tiles<OP_UNION, MODE_COUNT>(c, d_descs, d_tpair, d_ta0,
+                                               total_tiles, nullptr, 0, d_tcnt,
+                                               nullptr, nullptr);
+        }
+        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
 
-            u64 *d_part = nullptr;
-            if (!fused) {
-                if ((rc = run_scan(c, d_tcnt, total_tiles + 1, d_toff))) return rc;
-                d_part = (u64 *)c->ws[WS_PARTIAL];
-            }
+        u64 *d_part = nullptr;
+        if (!fused) {
+            if ((rc = run_scan(c, d_tcnt, total_tiles + 1, d_toff))) return rc;
+            d_part = (u64 *)c->ws[WS_PARTIAL];
+        }
 
-            if (fused) {
-                /* WS_POUT is reused between calls and zero-tile pairs get no
-                 * chunk: their length must read 0 */
-                HIP_TRY(hipMemsetAsync(d_pout, 0, (size_t)n_pairs * sizeof(u64),
-                                       c->stream));
-                hipLaunchKernelGGL(k_tail_fused, dim3((u32)(cmap.size() - 1)),
-                                   dim3(UA_BLOCK), 0, c->stream, d_descs, d_cmap,
-                                   d_tcnt, d_stage, stage_stride, prim, d_pout, op);
-            } else if (op == OP_UNION) {
-                two_kernels = true;
-                HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-                launch_tiles<OP_UNION, MODE_WRITE>(c, d_descs, d_tpair, d_ta0,
-                                                   total_tiles, nullptr, 0, d_tcnt,
-                                                   d_toff, d_part);
-                HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-            } else {
-                u64 cblk = (total_tiles + 15) / 16;
-                hipLaunchKernelGGL(k_compact, dim3((u32)cblk), dim3(UA_BLOCK), 0,
-                                   c->stream, d_descs, d_tpair, d_tb, d_tcnt, d_toff,
-                                   d_part, d_stage, stage_stride, prim, total_tiles,
-                                   op);
-                u64 sblk = (total_tiles + UA_BLOCK - 1) / UA_BLOCK;
-                hipLaunchKernelGGL(k_compact_small, dim3((u32)sblk), dim3(UA_BLOCK),
-                                   0, c->stream, d_descs, d_tpair, d_tb, d_tcnt,
-                                   d_toff, d_part, d_stage, stage_stride, prim,
-                                   total_tiles, op);
-            }
-            if (!fused) {
-                u64 poutblk = ((u64)n_pairs + UA_BLOCK - 1) / UA_BLOCK;
-                hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0,
-                                   c->stream, d_toff, d_part, d_tb, n_pairs, d_pout);
-            }
+        if (fused) {
+            /* WS_POUT is reused between calls and zero-tile pairs get no
+             * chunk: their length must read 0 */
+            HIP_TRY(hipMemsetAsync(d_pout, 0, (size_t)n_pairs * sizeof(u64),
+                                   c->stream));
+            hipLaunchKernelGGL(k_tail_fused, dim3((u32)(cmap.size() - 1)),
+                               dim3(UA_BLOCK), 0, c->stream, d_descs, d_cmap,
+                               d_tcnt, d_stage, stage_stride, prim, d_pout, op);
+        } else if (op == OP_UNION) {
+            two_kernels = true;
+            HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+            launch_tiles<OP_UNION, MODE_WRITE>(c, d_descs, d_tpair, d_ta0,
+                                               total_tiles, nullptr, 0, d_tcnt,
+                                               d_toff, d_part);
+            HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+        } else {
+            u64 cblk = (total_tiles + 15) / 16;
+            hipLaunchKernelGGL(k_compact, dim3((u32)cblk), dim3(UA_BLOCK), 0,
+                               c->stream, d_descs, d_tpair, d_tb, d_tcnt, d_toff,
+                               d_part, d_stage, stage_stride, prim, total_tiles,
+                               op);
+            u64 sblk = (total_tiles + UA_BLOCK - 1) / UA_BLOCK;
+            hipLaunchKernelGGL(k_compact_small, dim3((u32)sblk), dim3(UA_BLOCK),
+                               0, c->stream, d_descs, d_tpair, d_tb, d_tcnt,
+                               d_toff, d_part, d_stage, stage_stride, prim,
+                               total_tiles, op);
+        }
+        if (!fused) {
+            u64 poutblk = ((u64)n_pairs + UA_BLOCK - 1) / UA_BLOCK;
+            hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0,
+                               c->stream, d_toff, d_part, d_tb, n_pairs, d_pout);
         }
         HIP_TRY(hipMemcpyAsync(out_lens, d_pout, (size_t)n_pairs * sizeof(u64),
                                hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipGetLastError());
-        if (lb) {
-            /* pairs with zero tiles (n+m == 0) never publish a length */
-            for (int p = 0; p < n_pairs; p++)
-                if (pairs[p].n + pairs[p].m == 0) out_lens[p] = 0;
-        }
 
         /* stats: HIP-event time of the dominant (tile) kernel(s) */
         float ms = 0.f;
@@ -3561,20 +1954,12 @@ struct ua_batch {
     u64 *d_toff = nullptr;
     u64 *d_part = nullptr;
     u64 *d_pout = nullptr;
-    u64 *d_lbf = nullptr;    /* lookback flag array [total_tiles] */
-    u32 lb_gen = 0;
     /* cached per-thread merge-path splits (valid because the prepared
      * batch's inputs are immutable — same contract as the cached tile
-     * partition): u16 per (tile, thread); written by the first staged /
-     * lookback run, read by every later one */
+     * partition): u16 per (tile, thread); written by the first run, read by
+     * every later one */
     u32 *d_isplit = nullptr; /* packed lo16 = i0(s0), hi16 = i0b(smid) */
     bool i0_ready = false;
-    /* A-indexed layout for the wave-register intersect (k_aisect) */
-    u64 total_atiles = 0;
-    u64 nchunks_a = 0;
-    u32 *d_tpair_a = nullptr;
-    u64 *d_tba = nullptr;
-    u32 *d_bstart = nullptr;
     /* hipGraph capture of the staged pipeline (per op); out_lens land in the
      * pinned h_pout so the captured D2H copy has a fixed destination */
     hipGraphExec_t gexec[3][2] = {};
@@ -3604,17 +1989,6 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     tb[n_pairs] = b->total_tiles;
     u64 T = b->total_tiles;
     b->nchunks = (T + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
-    /* A-indexed tiles (wave-register intersect): tiles of UA_AT A-elems */
-    std::vector<u64> tba((size_t)n_pairs + 1);
-    for (int p = 0; p < n_pairs; p++) {
-        tba[p] = b->total_atiles;
-        b->total_atiles += (pairs[p].n + UA_AT - 1) / UA_AT;
-    }
-    tba[n_pairs] = b->total_atiles;
-    u64 Ta = b->total_atiles;
-    b->nchunks_a = (Ta + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
-    u64 Tmax = T > Ta ? T : Ta;
-    u64 ncmax = b->nchunks > b->nchunks_a ? b->nchunks : b->nchunks_a;
 
     std::vector<UaTChunk> cmap;
     const bool fused = T > 0 && fused_tail_enabled() &&
@@ -3625,16 +1999,12 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     size_t o_tb = align16(o_desc + descs.size() * sizeof(UaDesc));
     size_t o_cmap = align16(o_tb + tb.size() * sizeof(u64));
     size_t o_toff = align16(o_cmap + cmap.size() * sizeof(UaTChunk));
-    size_t o_part = align16(o_toff + (Tmax + 1) * sizeof(u64));
-    size_t o_pout = align16(o_part + (ncmax + 1) * sizeof(u64));
+    size_t o_part = align16(o_toff + (T + 1) * sizeof(u64));
+    size_t o_pout = align16(o_part + (b->nchunks + 1) * sizeof(u64));
     size_t o_tpair = align16(o_pout + (size_t)std::max(n_pairs, 1) * sizeof(u64));
     size_t o_ta0 = align16(o_tpair + (T + 1) * sizeof(u32));
     size_t o_tcnt = align16(o_ta0 + (T + 1) * sizeof(u32));
-    size_t o_lbf = align16(o_tcnt + (Tmax + 1) * sizeof(u32));
-    size_t o_tba = align16(o_lbf + (T + 1) * sizeof(u64));
-    size_t o_tpa = align16(o_tba + tba.size() * sizeof(u64));
-    size_t o_bst = align16(o_tpa + (Ta + 1) * sizeof(u32));
-    size_t total_bytes = align16(o_bst + (Ta + 1) * sizeof(u32));
+    size_t total_bytes = align16(o_tcnt + (T + 1) * sizeof(u32));
     hipError_t e = hipMalloc(&b->mem, total_bytes);
     if (e != hipSuccess) {
         g_last_hip = e;
@@ -3652,10 +2022,6 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     b->d_tpair = (u32 *)(base + o_tpair);
     b->d_ta0 = (u32 *)(base + o_ta0);
     b->d_tcnt = (u32 *)(base + o_tcnt);
-    b->d_lbf = (u64 *)(base + o_lbf);
-    b->d_tba = (u64 *)(base + o_tba);
-    b->d_tpair_a = (u32 *)(base + o_tpa);
-    b->d_bstart = (u32 *)(base + o_bst);
 
     /* descs, tb and the chunk map go up in one copy */
     std::vector<u8> hostbuf(o_cmap + cmap.size() * sizeof(UaTChunk));
@@ -3665,15 +2031,11 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
         memcpy(hostbuf.data() + o_cmap, cmap.data(), cmap.size() * sizeof(UaTChunk));
     HIP_TRY(hipMemcpyAsync(b->mem, hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b->d_tba, tba.data(), tba.size() * sizeof(u64),
-                           hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(b->d_tcnt + T, 0, sizeof(u32), c->stream));
-    HIP_TRY(hipMemsetAsync(b->d_tcnt + Ta, 0, sizeof(u32), c->stream));
     HIP_TRY(hipMemsetAsync(b->d_toff, 0, sizeof(u64), c->stream));
     HIP_TRY(hipMemsetAsync(b->d_part, 0, sizeof(u64), c->stream));
-    /* lookback flags + pout start zeroed (gen 0 never used; zero-tile pairs
-     * never publish a length and stay 0 from here) */
-    HIP_TRY(hipMemsetAsync(b->d_lbf, 0, (T + 1) * sizeof(u64), c->stream));
+    /* pout starts zeroed: zero-tile pairs get no fused-tail chunk, never
+     * publish a length and stay 0 from here */
     HIP_TRY(hipMemsetAsync(b->d_pout, 0,
                            (size_t)std::max(n_pairs, 1) * sizeof(u64), c->stream));
     if (T > 0) {
@@ -3684,12 +2046,6 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
                            b->d_descs, b->d_tb, n_pairs, T, b->d_tpair, b->d_ta0, 0);
         hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
                            b->d_descs, b->d_tb, n_pairs, T, b->d_tpair, b->d_ta0, 1);
-    }
-    if (Ta > 0) {
-        u64 pblk = (Ta + UA_BLOCK - 1) / UA_BLOCK;
-        hipLaunchKernelGGL(k_apartition, dim3((u32)pblk), dim3(UA_BLOCK), 0,
-                           c->stream, b->d_descs, b->d_tba, n_pairs, Ta,
-                           b->d_tpair_a, b->d_bstart);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
@@ -3724,25 +2080,10 @@ extern "C" void ua_batch_destroy(ua_ctx *c, ua_batch *b) {
                     * this ROCm.  0 = eager launches */
 #endif
 
-/* the staged TILE kernel (eager, event-timed) */
-/* wave-register intersect path toggle (UA_AISECT=0 disables) */
-static int aisect_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("UA_AISECT");
-        v = (e && e[0]) ? (e[0] != '0') : 0;
-    }
-    return v;
-}
-
 /* lazy split-cache: returns (isin, isout) for this run and flips i0_ready */
 static void batch_isplit(ua_batch *b, const u32 **isin, u32 **isout) {
     *isin = nullptr;
     *isout = nullptr;
-    /* the experimental kernels neither store nor read the PACKED cache —
-     * engaging i0_ready with them active would hand a later default run an
-     * unwritten buffer */
-    if (pp_enabled() || rp_enabled()) return;
     if (!b->d_isplit) {
         size_t bytes = (size_t)b->total_tiles * UA_TBLOCK * sizeof(u32);
         if (bytes == 0 || hipMalloc((void **)&b->d_isplit, bytes) != hipSuccess) {
@@ -3758,42 +2099,22 @@ static void batch_isplit(ua_batch *b, const u32 **isin, u32 **isout) {
     }
 }
 
+/* the staged TILE kernel (eager, event-timed) */
 static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
                            bool record_events, int set) {
     u64 T = b->total_tiles;
     u64 *stage = set ? b->d_stage1 : b->d_stage;
     u32 *tcnt = set ? b->d_tcnt1 : b->d_tcnt;
-    /* the A-indexed kernel neither reads nor writes the split cache: take its
-     * early return BEFORE batch_isplit flips i0_ready, or a later merge-tile
-     * run would read splits nobody stored */
-    if ((kop == OP_INTERSECT || kop == OP_DIFF) && aisect_enabled() &&
-        b->total_atiles > 0) {
-        u64 Ta = b->total_atiles;
-        u64 blk = (Ta + (UA_BLOCK / 64) - 1) / (UA_BLOCK / 64);
-        if (record_events) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        if (kop == OP_INTERSECT)
-            hipLaunchKernelGGL(k_aisect<OP_INTERSECT>, dim3((u32)blk),
-                               dim3(UA_BLOCK), 0, c->stream, b->d_descs,
-                               b->d_tpair_a, b->d_tba, b->d_bstart, Ta, stage,
-                               tcnt);
-        else
-            hipLaunchKernelGGL(k_aisect<OP_DIFF>, dim3((u32)blk), dim3(UA_BLOCK),
-                               0, c->stream, b->d_descs, b->d_tpair_a, b->d_tba,
-                               b->d_bstart, Ta, stage, tcnt);
-        if (record_events) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-        return UA_OK;
-    }
     const u32 *isin;
     u32 *isout;
     batch_isplit(b, &isin, &isout);
     if (record_events) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     /* dense primary staging rides the (otherwise unused) offs arg of the
-     * STAGE launch; only for the default kernel and set 0 (overlap keeps
-     * the overflow-only layout, and the experimental kernels ignore it).
+     * STAGE launch; only for set 0 (overlap keeps the overflow-only layout).
      * One allocation attempt per batch: a failure is recorded, not retried,
      * so prim is the same on every run and in every captured tail. */
     const u64 *prim = nullptr;
-    if (set == 0 && !pp_enabled() && !rp_enabled() && kop != OP_UNION) {
+    if (set == 0 && kop != OP_UNION) {
         if (!b->stage_p_tried) {
             b->stage_p_tried = true;
             size_t pbytes = (size_t)(T ? T : 1) * UA_STAGE_P * sizeof(u64);
@@ -3822,32 +2143,24 @@ static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
 }
 
 /* the aux tail, leaving the pair lengths in d_pout (the caller copies them
- * to the host once, after the last pass).  Intersect/diff on the merge-tile
- * layout: ONE k_tail_fused.  Otherwise scan + write/compact + pair_out.
+ * to the host once, after the last pass).  Intersect/diff within the chunk
+ * limit: ONE k_tail_fused.  Otherwise scan + write/compact + pair_out.
  * Captured into a hipGraph for intersect/diff; union's WRITE pass is a
  * second tile kernel that needs live events, so union stays eager
  * throughout. */
 static int batch_tail_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
                           bool record_events, int set, hipStream_t st) {
-    /* active tile layout: the A-indexed one when the wave-register
-     * intersect produced the counts (intersect/diff with UA_AISECT) */
-    bool aA = (kop != OP_UNION) && aisect_enabled() && b->total_atiles > 0;
-    if (kop != OP_UNION && !aA && b->n_tchunks > 0) {
-        /* set 1 (overlap) has no primary region: prim == nullptr */
-        const u64 *prim = (set == 0 && !pp_enabled() && !rp_enabled())
-                              ? b->d_stage_p
-                              : nullptr;
+    /* set 1 (overlap) has no primary region: prim == nullptr */
+    const u64 *prim = (set == 0) ? b->d_stage_p : nullptr;
+    if (kop != OP_UNION && b->n_tchunks > 0) {
         hipLaunchKernelGGL(k_tail_fused, dim3((u32)b->n_tchunks), dim3(UA_BLOCK), 0,
                            st, b->d_descs, b->d_cmap, set ? b->d_tcnt1 : b->d_tcnt,
                            set ? b->d_stage1 : b->d_stage, stride, prim, b->d_pout,
                            kop);
         return UA_OK;
     }
-    u64 T = aA ? b->total_atiles : b->total_tiles;
-    u64 nch = aA ? b->nchunks_a : b->nchunks;
-    const u32 *tpair = aA ? b->d_tpair_a : b->d_tpair;
-    const u64 *tbx = aA ? b->d_tba : b->d_tb;
-    u64 stride_x = aA ? (u64)UA_AT : stride;
+    u64 T = b->total_tiles;
+    u64 nch = b->nchunks;
     u32 *tcnt = set ? b->d_tcnt1 : b->d_tcnt;
     u64 *toff = set ? b->d_toff1 : b->d_toff;
     u64 *part = set ? b->d_part1 : b->d_part;
@@ -3865,19 +2178,16 @@ static int batch_tail_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
                                            b->d_part, isw, nullptr);
         if (record_events) HIP_TRY(hipEventRecord(c->ev[3], st));
     } else {
-        const u64 *prim = (set == 0 && !pp_enabled() && !rp_enabled())
-                              ? b->d_stage_p
-                              : nullptr;
         hipLaunchKernelGGL(k_compact, dim3((u32)((T + 15) / 16)), dim3(UA_BLOCK), 0,
-                           st, b->d_descs, tpair, tbx, tcnt, toff,
-                           part, stage, stride_x, prim, T, kop);
+                           st, b->d_descs, b->d_tpair, b->d_tb, tcnt, toff,
+                           part, stage, stride, prim, T, kop);
         hipLaunchKernelGGL(k_compact_small, dim3((u32)((T + UA_BLOCK - 1) / UA_BLOCK)),
-                           dim3(UA_BLOCK), 0, st, b->d_descs, tpair, tbx, tcnt,
-                           toff, part, stage, stride_x, prim, T, kop);
+                           dim3(UA_BLOCK), 0, st, b->d_descs, b->d_tpair, b->d_tb, tcnt,
+                           toff, part, stage, stride, prim, T, kop);
     }
     u64 poutblk = ((u64)b->n_pairs + UA_BLOCK - 1) / UA_BLOCK;
     hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, st,
-                       toff, part, tbx, b->n_pairs, b->d_pout);
+                       toff, part, b->d_tb, b->n_pairs, b->d_pout);
     return UA_OK;
 }
 
@@ -3964,138 +2274,95 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
         for (int p = 0; p < b->n_pairs; p++) out_lens[p] = 0;
         return UA_OK;
     }
-    const bool lb = (kop == OP_UNION) ? (bool)UA_LOOKBACK_UNION : (bool)UA_LOOKBACK;
-    bool two_kernels = false;
+    const bool two_kernels = (kop == OP_UNION);
     int rc;
-    if (lb) {
+    u64 stride = (kop == OP_INTERSECT) ? UA_TILE / 2 : UA_TILE;
+    if (kop != OP_UNION && !b->d_stage) {
+        hipError_t e = hipMalloc((void **)&b->d_stage,
+                                 (T ? T : 1) * UA_TILE * sizeof(u64));
+        if (e != hipSuccess) {
+            g_last_hip = e;
+            return UA_ERR_NOMEM;
+        }
+    }
+    if (!b->h_pout) {
+        hipError_t e = hipHostMalloc((void **)&b->h_pout,
+                                     (size_t)b->n_pairs * sizeof(u64));
+        if (e != hipSuccess) {
+            g_last_hip = e;
+            return UA_ERR_NOMEM;
+        }
+    }
+    /* overlapped serving shape (UA_OVERLAP=1, measured NEUTRAL and
+     * default-off): the aux tail (scan/compact/pair_out) of run i
+     * executes on the tail stream against buffer set i&1 while run
+     * i+1's tile kernel fills the other set.  Parity-green, but
+     * co-scheduling contention stretches the tile kernel (727->766 us)
+     * and k_compact (64->90 us) by about what the overlap hides —
+     * whole-step 0.813 vs 0.802 ms serial, with one box showing a
+     * pathological 1.65 ms at long run counts.  Union always serial
+     * (its WRITE pass is a second tile kernel with live stats
+     * events). */
+    const char *ovl_env = getenv("UA_OVERLAP");
+    bool ovl = (kop != OP_UNION) && n_runs > 1 && c->stream_tail &&
+               ovl_env && ovl_env[0] == '1';
+    if (ovl && !b->mem1) {
+        size_t o_cnt1 = 0;
+        size_t o_off1 = align16(o_cnt1 + (T + 1) * sizeof(u32));
+        size_t o_part1 = align16(o_off1 + (T + 1) * sizeof(u64));
+        size_t tot1 = align16(o_part1 + (b->nchunks + 1) * sizeof(u64));
+        hipError_t e = hipMalloc(&b->mem1, tot1);
+        if (e == hipSuccess)
+            e = hipMalloc((void **)&b->d_stage1,
+                          (T ? T : 1) * UA_TILE * sizeof(u64));
+        if (e != hipSuccess) {
+            if (b->mem1) { (void)hipFree(b->mem1); b->mem1 = nullptr; }
+            ovl = false; /* fall back to the serial path */
+        } else {
+            u8 *m1 = (u8 *)b->mem1;
+            b->d_tcnt1 = (u32 *)(m1 + o_cnt1);
+            b->d_toff1 = (u64 *)(m1 + o_off1);
+            b->d_part1 = (u64 *)(m1 + o_part1);
+            HIP_TRY(hipMemsetAsync(b->d_tcnt1 + T, 0, sizeof(u32), c->stream));
+        }
+    } else if (ovl && !b->d_stage1) {
+        ovl = false;
+    }
+    if (ovl) {
         for (int it = 0; it < n_runs; it++) {
             bool rec = (it == n_runs - 1);
-            if (b->lb_gen >= UA_LB_GEN_MAX) {
-                HIP_TRY(hipMemsetAsync(b->d_lbf, 0, (T + 1) * sizeof(u64), c->stream));
-                b->lb_gen = 0;
-            }
-            b->lb_gen += 1;
-            u64 gen = b->lb_gen;
-            const u32 *isin;
-            u32 *isout;
-            batch_isplit(b, &isin, &isout);
-            if (rec) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-            if (kop == OP_INTERSECT) {
-                launch_tiles<OP_INTERSECT, MODE_LOOKBACK>(c, b->d_descs, b->d_tpair,
-                                                          b->d_ta0, T, b->d_lbf, gen,
-                                                          nullptr, b->d_pout, nullptr,
-                                                          isin, isout);
-            } else if (kop == OP_DIFF) {
-                launch_tiles<OP_DIFF, MODE_LOOKBACK>(c, b->d_descs, b->d_tpair,
-                                                     b->d_ta0, T, b->d_lbf, gen,
-                                                     nullptr, b->d_pout, nullptr,
-                                                     isin, isout);
-            } else {
-                launch_tiles<OP_UNION, MODE_LOOKBACK>(c, b->d_descs, b->d_tpair,
-                                                      b->d_ta0, T, b->d_lbf, gen,
-                                                      nullptr, b->d_pout, nullptr,
-                                                      isin, isout);
-            }
-            if (rec) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+            int s = it & 1;
+            /* set s's tail from run it-2 must be done before refilling */
+            HIP_TRY(hipStreamWaitEvent(c->stream, c->oev[2 + s], 0));
+            if ((rc = batch_tiles_seq(c, b, kop, stride, rec, s))) return rc;
+            HIP_TRY(hipEventRecord(c->oev[s], c->stream));
+            HIP_TRY(hipStreamWaitEvent(c->stream_tail, c->oev[s], 0));
+            if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, s,
+                                          c->stream_tail)))
+                return rc;
+            HIP_TRY(hipEventRecord(c->oev[2 + s], c->stream_tail));
         }
-        HIP_TRY(hipMemcpyAsync(out_lens, b->d_pout, (size_t)b->n_pairs * sizeof(u64),
+        /* lengths: one copy after the last pass (only the last pass's
+         * are returned); tails are serialized on the tail stream */
+        HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
+                               (size_t)b->n_pairs * sizeof(u64),
+                               hipMemcpyDeviceToHost, c->stream_tail));
+        HIP_TRY(hipStreamSynchronize(c->stream_tail));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+        for (int it = 0; it < n_runs; it++) {
+            bool rec = (it == n_runs - 1);
+            if ((rc = batch_tiles_seq(c, b, kop, stride, rec, 0))) return rc;
+            if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, 0, c->stream)))
+                return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
+                               (size_t)b->n_pairs * sizeof(u64),
                                hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipGetLastError());
-        /* zero-tile pairs stay 0 from the create-time d_pout memset */
-    } else {
-        two_kernels = (kop == OP_UNION);
-        u64 stride = (kop == OP_INTERSECT) ? UA_TILE / 2 : UA_TILE;
-        if (kop != OP_UNION && !b->d_stage) {
-            hipError_t e = hipMalloc((void **)&b->d_stage,
-                                     (T ? T : 1) * UA_TILE * sizeof(u64));
-            if (e != hipSuccess) {
-                g_last_hip = e;
-                return UA_ERR_NOMEM;
-            }
-        }
-        if (!b->h_pout) {
-            hipError_t e = hipHostMalloc((void **)&b->h_pout,
-                                         (size_t)b->n_pairs * sizeof(u64));
-            if (e != hipSuccess) {
-                g_last_hip = e;
-                return UA_ERR_NOMEM;
-            }
-        }
-        /* overlapped serving shape (UA_OVERLAP=1, measured NEUTRAL and
-         * default-off): the aux tail (scan/compact/pair_out) of run i
-         * executes on the tail stream against buffer set i&1 while run
-         * i+1's tile kernel fills the other set.  Parity-green, but
-         * co-scheduling contention stretches the tile kernel (727->766 us)
-         * and k_compact (64->90 us) by about what the overlap hides —
-         * whole-step 0.813 vs 0.802 ms serial, with one box showing a
-         * pathological 1.65 ms at long run counts.  Union always serial
-         * (its WRITE pass is a second tile kernel with live stats
-         * events). */
-        const char *ovl_env = getenv("UA_OVERLAP");
-        bool ovl = (kop != OP_UNION) && n_runs > 1 && c->stream_tail &&
-                   ovl_env && ovl_env[0] == '1';
-        /* the set-1 buffers below are sized for the merge-tile layout
-         * (total_tiles / nchunks); the A-indexed layout can need more */
-        if (aisect_enabled()) ovl = false;
-        if (ovl && !b->mem1) {
-            size_t o_cnt1 = 0;
-            size_t o_off1 = align16(o_cnt1 + (T + 1) * sizeof(u32));
-            size_t o_part1 = align16(o_off1 + (T + 1) * sizeof(u64));
-            size_t tot1 = align16(o_part1 + (b->nchunks + 1) * sizeof(u64));
-            hipError_t e = hipMalloc(&b->mem1, tot1);
-            if (e == hipSuccess)
-                e = hipMalloc((void **)&b->d_stage1,
-                              (T ? T : 1) * UA_TILE * sizeof(u64));
-            if (e != hipSuccess) {
-                if (b->mem1) { (void)hipFree(b->mem1); b->mem1 = nullptr; }
-                ovl = false; /* fall back to the serial path */
-            } else {
-                u8 *m1 = (u8 *)b->mem1;
-                b->d_tcnt1 = (u32 *)(m1 + o_cnt1);
-                b->d_toff1 = (u64 *)(m1 + o_off1);
-                b->d_part1 = (u64 *)(m1 + o_part1);
-                HIP_TRY(hipMemsetAsync(b->d_tcnt1 + T, 0, sizeof(u32), c->stream));
-            }
-        } else if (ovl && !b->d_stage1) {
-            ovl = false;
-        }
-        if (ovl) {
-            for (int it = 0; it < n_runs; it++) {
-                bool rec = (it == n_runs - 1);
-                int s = it & 1;
-                /* set s's tail from run it-2 must be done before refilling */
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->oev[2 + s], 0));
-                if ((rc = batch_tiles_seq(c, b, kop, stride, rec, s))) return rc;
-                HIP_TRY(hipEventRecord(c->oev[s], c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->stream_tail, c->oev[s], 0));
-                if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, s,
-                                              c->stream_tail)))
-                    return rc;
-                HIP_TRY(hipEventRecord(c->oev[2 + s], c->stream_tail));
-            }
-            /* lengths: one copy after the last pass (only the last pass's
-             * are returned); tails are serialized on the tail stream */
-            HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
-                                   (size_t)b->n_pairs * sizeof(u64),
-                                   hipMemcpyDeviceToHost, c->stream_tail));
-            HIP_TRY(hipStreamSynchronize(c->stream_tail));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        } else {
-            for (int it = 0; it < n_runs; it++) {
-                bool rec = (it == n_runs - 1);
-                if ((rc = batch_tiles_seq(c, b, kop, stride, rec, 0))) return rc;
-                if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, 0, c->stream)))
-                    return rc;
-            }
-            HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
-                                   (size_t)b->n_pairs * sizeof(u64),
-                                   hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        HIP_TRY(hipGetLastError());
-        memcpy(out_lens, b->h_pout, (size_t)b->n_pairs * sizeof(u64));
     }
+    HIP_TRY(hipGetLastError());
+    memcpy(out_lens, b->h_pout, (size_t)b->n_pairs * sizeof(u64));
 
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) {
@@ -4247,12 +2514,12 @@ extern "C" int ua_apply_filter_batch_dev(ua_ctx *c, const ua_dfilter *tasks,
     HIP_TRY(hipMemcpyAsync(d_descs, hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
     if (T > 0) {
-        u64 *d_lbf;
+        u64 *d_look;
         u64 gen;
-        if ((rc = lb_acquire_ws(c, T, &d_lbf, &gen))) return rc;
+        if ((rc = lb_acquire_ws(c, T, &d_look, &gen))) return rc;
         HIP_TRY(hipEventRecord(c->ev[0], c->stream));
         hipLaunchKernelGGL(k_filter, dim3((u32)T), dim3(UA_BLOCK), 0, c->stream,
-                           d_descs, d_tb, n_tasks, T, d_lbf, gen, d_pout);
+                           d_descs, d_tb, n_tasks, T, d_look, gen, d_pout);
         HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     }
     HIP_TRY(hipMemcpyAsync(out_lens, d_pout, (size_t)n_tasks * sizeof(u64),
@@ -4463,19 +2730,11 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     if ((rc = ws_reserve(c, WS_TOFF, (max_tiles + 1) * sizeof(u64)))) return rc;
     u64 max_chunks = (max_tiles + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
     if ((rc = ws_reserve(c, WS_PARTIAL, (max_chunks + 1) * sizeof(u64)))) return rc;
-#if UA_LOOKBACK_UNION
-    /* pre-size the lookback flag array so per-round acquires never realloc
-     * mid-enqueue (hipFree would drain the stream) */
-    if ((rc = ws_reserve(c, WS_LBF, (max_tiles + 1) * sizeof(u64)))) return rc;
-#endif
     u32 *d_tpair = (u32 *)c->ws[WS_TPAIR];
     u32 *d_ta0 = (u32 *)c->ws[WS_TA0];
     u32 *d_tcnt = (u32 *)c->ws[WS_TCNT];
     u64 *d_toff = (u64 *)c->ws[WS_TOFF];
     u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
-    (void)d_tcnt;
-    (void)d_toff;
-    (void)d_part;
 
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     int lcur = 0;
@@ -4487,24 +2746,6 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
         u64 mk = ((u64)rd.npair + UA_BLOCK - 1) / UA_BLOCK;
         hipLaunchKernelGGL(k_make_descs, dim3((u32)mk), dim3(UA_BLOCK), 0, c->stream,
                            d_descs, d_lens[lcur], rd.nk_prev, rd.npair);
-#if UA_LOOKBACK_UNION
-        /* zero-capacity pairs have no tiles and never publish a length */
-        HIP_TRY(hipMemsetAsync(d_lens[lcur ^ 1], 0, (size_t)rd.npair * sizeof(u64),
-                               c->stream));
-        if (T > 0) {
-            u64 pblk = (T + UA_BLOCK - 1) / UA_BLOCK;
-            hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                               d_descs, d_tb, rd.npair, T, d_tpair, d_ta0, 0);
-            hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                               d_descs, d_tb, rd.npair, T, d_tpair, d_ta0, 1);
-            u64 *d_lbf;
-            u64 gen;
-            if ((rc = lb_acquire_ws(c, T, &d_lbf, &gen))) return rc;
-            launch_tiles<OP_UNION, MODE_LOOKBACK>(c, d_descs, d_tpair, d_ta0, T,
-                                                  d_lbf, gen, nullptr,
-                                                  d_lens[lcur ^ 1], nullptr);
-        }
-#else
         HIP_TRY(hipMemsetAsync(d_tcnt + T, 0, sizeof(u32), c->stream));
         if (T > 0) {
             u64 pblk = (T + UA_BLOCK - 1) / UA_BLOCK;
@@ -4528,7 +2769,6 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
         u64 poutblk = ((u64)rd.npair + UA_BLOCK - 1) / UA_BLOCK;
         hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, c->stream,
                            d_toff, d_part, d_tb, rd.npair, d_lens[lcur ^ 1]);
-#endif
         lcur ^= 1;
     }
     /* final item: data in ptrs[0] (capacity position), length in d_lens[lcur][0] */
@@ -4546,13 +2786,8 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->kernel_ms += ms;
-#if UA_LOOKBACK_UNION
-    c->n_launches += R;
-    c->bytes_algo += 8 * 2 * cap_work; /* capacity upper bound (in + out, one pass) */
-#else
     c->n_launches += 2 * R;
     c->bytes_algo += 8 * 3 * cap_work; /* capacity upper bound (union count+write) */
-#endif
     *out_n = final_len;
     return UA_OK;
 }

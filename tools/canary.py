@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fast engine canary for fresh GPU boxes: one small pass over every lookback
+"""Fast engine canary for fresh GPU boxes: one small pass over every batched
 code path (one-shot batch, prepared batch, union, difference, merge tree,
 apply_filter, sort segments) with correctness asserts.  Run under `timeout`
 FIRST on a box so a regression hangs this tiny probe, not the full suite."""
@@ -37,7 +37,7 @@ def main():
     assert lens[0] == np.union1d(u, v).size
     outs, lens = eng.difference_pairs(us, vs)
     assert lens[0] == np.setdiff1d(u, v).size
-    # prepared batch incl. a 1Mx1M pair (multi-tile lookback chains)
+    # prepared batch incl. a 1Mx1M pair (many tiles and tail chunks per pair)
     u0, v0, common0 = synth.gen_pair(rng, 1_000_000, 1_000_000, 10_000,
                                      100_000_000)
     du, dv = dev(u0), dev(v0)
