@@ -605,7 +605,7 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         /* clamp to the staging stride: invalid (duplicate/unsorted) inputs
          * can emit more than stride entries per tile; results there are
          * unspecified, OOB writes are not.  Small totals go to
-         * the dense primary region (offs = its base, see batch_tiles_seq);
+         * the dense primary region (offs = its base, see enqueue_tiles);
          * stage_stride stays the sparse overflow. */
         bool prim = (offs != nullptr) && (total <= UA_STAGE_P);
         u32 cap_t = prim ? (u32)UA_STAGE_P : (u32)stage_stride;
@@ -1540,14 +1540,9 @@ extern "C" const char *ua_strerror(int code) {
 
 extern "C" int ua_version(void) { return 11; }
 
-extern "C" int ua_ctx_create(ua_ctx **out, int device) {
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) return UA_ERR_NO_GPU;
-    if (device < 0 || device >= ndev) return UA_ERR_INVALID;
-    ua_ctx *c = new ua_ctx();
-    c->device = device;
-    HIP_TRY(hipSetDevice(device));
+/* streams and events; on failure the caller destroys c */
+static int ctx_init(ua_ctx *c) {
+    HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamCreate(&c->stream));
     for (int i = 0; i < 4; i++) {
         HIP_TRY(hipEventCreate(&c->ev[i]));
@@ -1559,6 +1554,21 @@ extern "C" int ua_ctx_create(ua_ctx **out, int device) {
     for (int i = 0; i < 4; i++)
         HIP_TRY(hipEventCreateWithFlags(&c->oev[i], hipEventDisableTiming));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return UA_OK;
+}
+
+extern "C" int ua_ctx_create(ua_ctx **out, int device) {
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev == 0) return UA_ERR_NO_GPU;
+    if (device < 0 || device >= ndev) return UA_ERR_INVALID;
+    ua_ctx *c = new ua_ctx();
+    c->device = device;
+    int rc = ctx_init(c);
+    if (rc) {
+        ua_ctx_destroy(c);
+        return rc;
+    }
     *out = c;
     return UA_OK;
 }
@@ -1568,6 +1578,7 @@ extern "C" void ua_ctx_destroy(ua_ctx *c) {
     (void)hipSetDevice(c->device);
     for (int i = 0; i < WS_COUNT; i++)
         if (c->ws[i]) (void)hipFree(c->ws[i]);
+    if (c->d_viol) (void)hipFree(c->d_viol);
     for (int i = 0; i < 4; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 4; i++)
@@ -1666,28 +1677,138 @@ extern "C" int ua_stats_get(ua_ctx *c, uint64_t *n_launches, double *kernel_ms,
     return UA_OK;
 }
 
-/* one workgroup per tile on the main stream; isin/isout are the prepared
- * batch's cached merge-path splits (see k_tiles) */
-template <int OP, int MODE>
-static void launch_tiles(ua_ctx *c, const UaDesc *descs, const u32 *tpair,
-                         const u32 *ta0, u64 T, u64 *stage, u64 stride, u32 *tcnt,
-                         const u64 *offs, const u64 *part,
-                         const u32 *isin = nullptr, u32 *isout = nullptr) {
-    hipLaunchKernelGGL((k_tiles<OP, MODE>), dim3((u32)T), dim3(UA_TBLOCK), 0, c->stream,
-                       descs, tpair, ta0, T, stage, stride, tcnt, offs, part,
-                       isin, isout);
+/* stats: one HIP-event pair -> kernel_ms, counted as n sampled launches */
+static int stats_add(ua_ctx *c, hipEvent_t e0, hipEvent_t e1, u64 n = 1) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    c->kernel_ms += ms;
+    c->n_launches += n;
+    return UA_OK;
 }
 
-/* Split flat scan: offs_dev gets chunk-local exclusive offsets, WS_PARTIAL
- * gets the scanned chunk partials; consumers combine via d_off(). */
-static int run_scan(ua_ctx *c, const u32 *cnt_dev, u64 n, u64 *offs_dev) {
-    u64 nchunks = (n + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
+static u64 scan_chunks(u64 n) { return (n + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK; }
+
+/* Split flat scan: offs gets chunk-local exclusive offsets, part the scanned
+ * chunk partials (nchunks + 1 u64); consumers combine via d_off(). */
+static void enqueue_scan(const u32 *cnt, u64 n, u64 *offs, u64 *part, u64 nchunks,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(k_scan1, dim3((u32)nchunks), dim3(UA_BLOCK), 0, st, cnt, n, offs,
+                       part);
+    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(UA_BLOCK), 0, st, part, nchunks);
+}
+
+/* the scan on the ctx stream with its partials in WS_PARTIAL */
+static int ws_scan(ua_ctx *c, const u32 *cnt, u64 n, u64 *offs) {
+    u64 nchunks = scan_chunks(n);
     int rc = ws_reserve(c, WS_PARTIAL, (nchunks + 1) * sizeof(u64));
     if (rc) return rc;
-    u64 *partials = (u64 *)c->ws[WS_PARTIAL];
-    hipLaunchKernelGGL(k_scan1, dim3((u32)nchunks), dim3(UA_BLOCK), 0, c->stream,
-                       cnt_dev, n, offs_dev, partials);
-    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(UA_BLOCK), 0, c->stream, partials, nchunks);
+    enqueue_scan(cnt, n, offs, (u64 *)c->ws[WS_PARTIAL], nchunks, c->stream);
+    return UA_OK;
+}
+
+/* ---- the pair pipeline: one view, one function per stage ----
+ *
+ * UaPipe is one pipeline instance as the kernels see it: plain pointers and
+ * counts, owning nothing.  Three owners fill one: the one-shot path from the
+ * ctx workspace, ua_batch from its own allocation (one view per buffer set)
+ * and ua_merge_k_dev once per round.  The enqueue_* functions below are the
+ * only place a pipeline kernel is launched and the only place the order
+ * partition -> tiles -> tail is written. */
+struct UaPipe {
+    UaDesc *descs = nullptr;
+    const u64 *tb = nullptr; /* per-pair first tile, n_pairs + 1 entries */
+    int n_pairs = 0;
+    u64 T = 0;               /* total tiles */
+    u32 *tpair = nullptr;    /* k_partition's output: tile -> pair ... */
+    u32 *ta0 = nullptr;      /* ... and tile -> first A index */
+    u32 *tcnt = nullptr;     /* T + 1 counts; the owner zeroes [T] */
+    u64 *toff = nullptr;     /* scanned tail: chunk-local offsets, T + 1 */
+    u64 *part = nullptr;     /* scanned tail: chunk partials, nchunks + 1 */
+    u64 nchunks = 0;         /* scan chunks over the T + 1 counts */
+    u64 *stage = nullptr;    /* staged ops: stage_stride(op) u64 per tile */
+    const u64 *prim = nullptr; /* dense primary staging (UA_STAGE_P/tile) or null */
+    const UaTChunk *cmap = nullptr; /* fused tail's chunk map */
+    u64 n_tchunks = 0;       /* 0 = this instance keeps the scanned tail */
+    u64 *pout = nullptr;     /* per-pair output lengths */
+};
+
+/* staging u64 per tile; 0 = the op does not stage (union, merge-all) */
+static u64 stage_stride(int op) {
+    return op == OP_INTERSECT ? UA_TILE / 2 : op == OP_DIFF ? UA_TILE : 0;
+}
+
+/* the two k_partition passes (T > 0) */
+static void enqueue_partition(const UaPipe &p, hipStream_t st) {
+    u64 pblk = (p.T + UA_BLOCK - 1) / UA_BLOCK;
+    for (int phase = 0; phase < 2; phase++)
+        hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, st, p.descs,
+                           p.tb, p.n_pairs, p.T, p.tpair, p.ta0, phase);
+}
+
+/* One workgroup per tile (T > 0).  STAGE passes the dense primary staging in
+ * the otherwise unused offs slot; only WRITE reads offs/partials.  isin/isout
+ * are the prepared batch's cached merge-path splits (see k_tiles). */
+static int enqueue_tiles(const UaPipe &p, int op, int mode, const u32 *isin, u32 *isout,
+                         hipStream_t st) {
+    void (*k)(const UaDesc *, const u32 *, const u32 *, u64, u64 *, u64, u32 *,
+              const u64 *, const u64 *, const u32 *, u32 *) = nullptr;
+    if (op == OP_INTERSECT && mode == MODE_STAGE) k = k_tiles<OP_INTERSECT, MODE_STAGE>;
+    else if (op == OP_DIFF && mode == MODE_STAGE) k = k_tiles<OP_DIFF, MODE_STAGE>;
+    else if (op == OP_UNION && mode == MODE_COUNT) k = k_tiles<OP_UNION, MODE_COUNT>;
+    else if (op == OP_UNION && mode == MODE_WRITE) k = k_tiles<OP_UNION, MODE_WRITE>;
+    else if (op == OP_MERGE_ALL && mode == MODE_DIRECT) k = k_tiles<OP_MERGE_ALL, MODE_DIRECT>;
+    else return UA_ERR_INVALID;
+    const bool staged = (mode == MODE_STAGE), write = (mode == MODE_WRITE);
+    hipLaunchKernelGGL(k, dim3((u32)p.T), dim3(UA_TBLOCK), 0, st, p.descs, p.tpair, p.ta0,
+                       p.T, staged ? p.stage : nullptr, stage_stride(op), p.tcnt,
+                       staged ? p.prim : write ? p.toff : nullptr,
+                       write ? p.part : nullptr, isin, isout);
+    return UA_OK;
+}
+
+/* the tile pass that opens each op's pipeline */
+static int first_mode(int op) {
+    return stage_stride(op) ? MODE_STAGE : op == OP_UNION ? MODE_COUNT : MODE_DIRECT;
+}
+
+/* The tail after the first tile pass, leaving the pair lengths in p.pout.
+ * Staged ops with a chunk map: ONE k_tail_fused (pairs without tiles get no
+ * chunk, so the owner zeroes pout).  Otherwise scan + (union: the WRITE tile
+ * pass, timed by ev[2]/ev[3] when asked | staged: compact) + k_pair_out.  A
+ * view without tiles (an all-empty round of the union tree) publishes zero
+ * lengths.  write_isin: cached splits for union's WRITE pass, or null. */
+static int enqueue_tail(ua_ctx *c, const UaPipe &p, int op, const u32 *write_isin,
+                        bool timed, hipStream_t st) {
+    const u64 stride = stage_stride(op);
+    if (op == OP_MERGE_ALL) return UA_OK; /* output position == path position */
+    if (stride && p.n_tchunks > 0) {
+        hipLaunchKernelGGL(k_tail_fused, dim3((u32)p.n_tchunks), dim3(UA_BLOCK), 0, st,
+                           p.descs, p.cmap, p.tcnt, p.stage, stride, p.prim, p.pout, op);
+        return UA_OK;
+    }
+    if (p.T == 0) {
+        HIP_TRY(hipMemsetAsync(p.toff, 0, sizeof(u64), st));
+        HIP_TRY(hipMemsetAsync(p.part, 0, sizeof(u64), st));
+    } else {
+        enqueue_scan(p.tcnt, p.T + 1, p.toff, p.part, p.nchunks, st);
+        if (op == OP_UNION) {
+            if (timed) HIP_TRY(hipEventRecord(c->ev[2], st));
+            int rc = enqueue_tiles(p, OP_UNION, MODE_WRITE, write_isin, nullptr, st);
+            if (rc) return rc;
+            if (timed) HIP_TRY(hipEventRecord(c->ev[3], st));
+        } else {
+            hipLaunchKernelGGL(k_compact, dim3((u32)((p.T + 15) / 16)), dim3(UA_BLOCK), 0,
+                               st, p.descs, p.tpair, p.tb, p.tcnt, p.toff, p.part,
+                               p.stage, stride, p.prim, p.T, op);
+            hipLaunchKernelGGL(k_compact_small,
+                               dim3((u32)((p.T + UA_BLOCK - 1) / UA_BLOCK)), dim3(UA_BLOCK),
+                               0, st, p.descs, p.tpair, p.tb, p.tcnt, p.toff, p.part,
+                               p.stage, stride, p.prim, p.T, op);
+        }
+    }
+    u64 poutblk = ((u64)p.n_pairs + UA_BLOCK - 1) / UA_BLOCK;
+    hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, st, p.toff,
+                       p.part, p.tb, p.n_pairs, p.pout);
     return UA_OK;
 }
 
@@ -1736,178 +1857,130 @@ static bool build_tail_chunks(const std::vector<u64> &tb, int n_pairs,
     return true;
 }
 
-/* ---- the batched set-algebra pipeline ---- */
+/* Host plan of one pair batch.  head is the upload image descs | tb | chunk
+ * map (one allocation, one copy); n_tchunks == 0 means the scanned tail:
+ * not asked for, toggled off, no tiles, or a pair over the chunk limit. */
+struct UaPlan {
+    std::vector<u8> head;
+    size_t o_tb = 0, o_cmap = 0; /* byte offsets into head */
+    u64 T = 0, in_bytes = 0, n_tchunks = 0;
+};
+
+static int plan_pairs(const ua_dpair *pairs, int n_pairs, bool want_fused, UaPlan &pl) {
+    if (n_pairs < 0) return UA_ERR_INVALID;
+    std::vector<UaDesc> descs((size_t)std::max(n_pairs, 1));
+    std::vector<u64> tb((size_t)n_pairs + 1);
+    for (int p = 0; p < n_pairs; p++) {
+        const ua_dpair &pr = pairs[p];
+        if (pr.n >= (1ull << 31) || pr.m >= (1ull << 31)) return UA_ERR_INVALID;
+        descs[p] = {pr.u, pr.n, pr.v, pr.m, pr.out, pl.T};
+        tb[p] = pl.T;
+        pl.T += (pr.n + pr.m + UA_TILE - 1) / UA_TILE;
+        pl.in_bytes += 8 * (pr.n + pr.m);
+    }
+    tb[n_pairs] = pl.T;
+    std::vector<UaTChunk> cmap;
+    if (want_fused && pl.T > 0 && fused_tail_enabled() &&
+        build_tail_chunks(tb, n_pairs, cmap))
+        pl.n_tchunks = cmap.size() - 1;
+    else
+        cmap.clear();
+    pl.o_tb = descs.size() * sizeof(UaDesc);
+    pl.o_cmap = align16(pl.o_tb + tb.size() * sizeof(u64));
+    pl.head.resize(pl.o_cmap + cmap.size() * sizeof(UaTChunk));
+    memcpy(pl.head.data(), descs.data(), pl.o_tb);
+    memcpy(pl.head.data() + pl.o_tb, tb.data(), tb.size() * sizeof(u64));
+    if (!cmap.empty())
+        memcpy(pl.head.data() + pl.o_cmap, cmap.data(), cmap.size() * sizeof(UaTChunk));
+    return UA_OK;
+}
+
+/* point a view at the device copy of a plan's head */
+static void pipe_set_head(UaPipe &p, const UaPlan &pl, int n_pairs, void *d_head) {
+    p.descs = (UaDesc *)d_head;
+    p.tb = (const u64 *)((u8 *)d_head + pl.o_tb);
+    p.cmap = (const UaTChunk *)((u8 *)d_head + pl.o_cmap);
+    p.n_pairs = n_pairs;
+    p.T = pl.T;
+    p.nchunks = scan_chunks(pl.T + 1);
+    p.n_tchunks = pl.n_tchunks;
+}
+
+/* ---- the batched set-algebra pipeline, one-shot on the ctx workspace ---- */
 static int run_batch_locked(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
                             uint64_t *out_lens, int op) {
     if (n_pairs <= 0) return UA_OK;
     HIP_TRY(hipSetDevice(c->device));
+    const u64 stride = stage_stride(op);
+    UaPlan pl;
+    int rc = plan_pairs(pairs, n_pairs, stride != 0, pl);
+    if (rc) return rc;
+    const u64 T = pl.T;
 
-    std::vector<UaDesc> descs((size_t)n_pairs);
-    std::vector<u64> tb((size_t)n_pairs + 1);
-    u64 total_tiles = 0;
-    u64 in_bytes = 0;
-    for (int p = 0; p < n_pairs; p++) {
-        const ua_dpair &pr = pairs[p];
-        if (pr.n >= (1ull << 31) || pr.m >= (1ull << 31)) return UA_ERR_INVALID;
-        descs[p] = {pr.u, pr.n, pr.v, pr.m, pr.out, total_tiles};
-        tb[p] = total_tiles;
-        total_tiles += (pr.n + pr.m + UA_TILE - 1) / UA_TILE;
-        in_bytes += 8 * (pr.n + pr.m);
-    }
-    tb[n_pairs] = total_tiles;
-
-    int rc;
-    /* fused tail: staged intersect/diff whose pairs all fit the chunk limit */
-    std::vector<UaTChunk> cmap;
-    const bool fused = (op == OP_INTERSECT || op == OP_DIFF) &&
-                       fused_tail_enabled() && build_tail_chunks(tb, n_pairs, cmap);
-    /* descs, tb and the tail's chunk map share one allocation and one upload */
-    size_t descs_bytes = descs.size() * sizeof(UaDesc);
-    size_t o_cmap = align16(descs_bytes + tb.size() * sizeof(u64));
-    size_t cmap_bytes = fused ? cmap.size() * sizeof(UaTChunk) : 0;
-    if ((rc = ws_reserve(c, WS_DESC, o_cmap + cmap_bytes))) return rc;
-    if ((rc = ws_reserve(c, WS_TPAIR, (total_tiles + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TA0, (total_tiles + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TCNT, (total_tiles + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TOFF, (total_tiles + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_DESC, pl.head.size()))) return rc;
+    if ((rc = ws_reserve(c, WS_TPAIR, (T + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TA0, (T + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TCNT, (T + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (T + 1) * sizeof(u64)))) return rc;
     if ((rc = ws_reserve(c, WS_POUT, (size_t)n_pairs * sizeof(u64)))) return rc;
-
-    u64 stage_stride = 0;
-    if (op == OP_INTERSECT) stage_stride = UA_TILE / 2;
-    else if (op == OP_DIFF) stage_stride = UA_TILE;
-    if (stage_stride) {
-        if ((rc = ws_reserve(c, WS_STAGE, total_tiles * stage_stride * sizeof(u64)))) return rc;
-        if ((rc = ws_reserve(c, WS_STAGEP, total_tiles * UA_STAGE_P * sizeof(u64)))) return rc;
+    if (stride) {
+        if ((rc = ws_reserve(c, WS_STAGE, T * stride * sizeof(u64)))) return rc;
+        if ((rc = ws_reserve(c, WS_STAGEP, T * UA_STAGE_P * sizeof(u64)))) return rc;
+    }
+    UaPipe p;
+    pipe_set_head(p, pl, n_pairs, c->ws[WS_DESC]);
+    if (T > 0 && op != OP_MERGE_ALL && !p.n_tchunks &&
+        (rc = ws_reserve(c, WS_PARTIAL, (p.nchunks + 1) * sizeof(u64))))
+        return rc;
+    p.tpair = (u32 *)c->ws[WS_TPAIR];
+    p.ta0 = (u32 *)c->ws[WS_TA0];
+    p.tcnt = (u32 *)c->ws[WS_TCNT];
+    p.toff = (u64 *)c->ws[WS_TOFF];
+    p.part = (u64 *)c->ws[WS_PARTIAL];
+    p.pout = (u64 *)c->ws[WS_POUT];
+    if (stride) {
+        p.stage = (u64 *)c->ws[WS_STAGE];
+        p.prim = (const u64 *)c->ws[WS_STAGEP];
     }
 
-    UaDesc *d_descs = (UaDesc *)c->ws[WS_DESC];
-    u64 *d_tb = (u64 *)((u8 *)c->ws[WS_DESC] + descs_bytes);
-    const UaTChunk *d_cmap = (const UaTChunk *)((u8 *)c->ws[WS_DESC] + o_cmap);
-    u32 *d_tpair = (u32 *)c->ws[WS_TPAIR];
-    u32 *d_ta0 = (u32 *)c->ws[WS_TA0];
-    u32 *d_tcnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_toff = (u64 *)c->ws[WS_TOFF];
-    u64 *d_pout = (u64 *)c->ws[WS_POUT];
-    u64 *d_stage = (u64 *)c->ws[WS_STAGE];
-
-    std::vector<u8> hostbuf(o_cmap + cmap_bytes);
-    memcpy(hostbuf.data(), descs.data(), descs_bytes);
-    memcpy(hostbuf.data() + descs_bytes, tb.data(), tb.size() * sizeof(u64));
-    if (fused) memcpy(hostbuf.data() + o_cmap, cmap.data(), cmap_bytes);
-    HIP_TRY(hipMemcpyAsync(d_descs, hostbuf.data(), hostbuf.size(),
-                           hipMemcpyHostToDevice, c->stream));
-    /* zero sentinel so offs[total_tiles] = total output */
-    HIP_TRY(hipMemsetAsync(d_tcnt + total_tiles, 0, sizeof(u32), c->stream));
-
-    if (total_tiles == 0) {
+    HIP_TRY(hipMemcpyAsync(p.descs, pl.head.data(), pl.head.size(), hipMemcpyHostToDevice,
+                           c->stream));
+    /* zero sentinel so offs[T] = total output */
+    HIP_TRY(hipMemsetAsync(p.tcnt + T, 0, sizeof(u32), c->stream));
+    if (T == 0) {
         /* every pair is empty (n+m == 0) */
-        HIP_TRY(hipStreamSynchronize(c->stream)); /* hostbuf is scoped */
-        for (int p = 0; p < n_pairs; p++) out_lens[p] = 0;
+        HIP_TRY(hipStreamSynchronize(c->stream)); /* pl.head is scoped */
+        for (int i = 0; i < n_pairs; i++) out_lens[i] = 0;
         return UA_OK;
     }
-    {
-        u64 pblk = (total_tiles + UA_BLOCK - 1) / UA_BLOCK;
-        hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                           d_descs, d_tb, n_pairs, total_tiles, d_tpair, d_ta0, 0);
-        hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                           d_descs, d_tb, n_pairs, total_tiles, d_tpair, d_ta0, 1);
-
-        if (op == OP_MERGE_ALL) {
-            /* duplicate-keeping merge: output position == path position, so no
-             * scan / staging / compaction / pair_out — lens are n+m */
-            HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-            launch_tiles<OP_MERGE_ALL, MODE_DIRECT>(c, d_descs, d_tpair, d_ta0,
-                                                    total_tiles, nullptr, 0, d_tcnt,
-                                                    nullptr, nullptr);
-            HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipGetLastError());
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            c->kernel_ms += ms;
-            c->n_launches += 1;
-            for (int p = 0; p < n_pairs; p++) out_lens[p] = pairs[p].n + pairs[p].m;
-            c->bytes_algo += 2 * in_bytes;
-            return UA_OK;
-        }
-
-        bool two_kernels = false;
-        const u64 *prim = (op != OP_UNION) ? (const u64 *)c->ws[WS_STAGEP] : nullptr;
-        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        if (op == OP_INTERSECT) {
-            launch_tiles<OP_INTERSECT, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
-                                                   total_tiles, d_stage,
-                                                   stage_stride, d_tcnt, prim,
-                                                   nullptr);
-        } else if (op == OP_DIFF) {
-            launch_tiles<OP_DIFF, MODE_STAGE>(c, d_descs, d_tpair, d_ta0,
-                                              total_tiles, d_stage, stage_stride,
-                                              d_tcnt, prim, nullptr);
-        } else {
-            launch_tiles<OP_UNION, MODE_COUNT>(c, d_descs, d_tpair, d_ta0,
-                                               total_tiles, nullptr, 0, d_tcnt,
-                                               nullptr, nullptr);
-        }
-        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-
-        u64 *d_part = nullptr;
-        if (!fused) {
-            if ((rc = run_scan(c, d_tcnt, total_tiles + 1, d_toff))) return rc;
-            d_part = (u64 *)c->ws[WS_PARTIAL];
-        }
-
-        if (fused) {
-            /* WS_POUT is reused between calls and zero-tile pairs get no
-             * chunk: their length must read 0 */
-            HIP_TRY(hipMemsetAsync(d_pout, 0, (size_t)n_pairs * sizeof(u64),
-                                   c->stream));
-            hipLaunchKernelGGL(k_tail_fused, dim3((u32)(cmap.size() - 1)),
-                               dim3(UA_BLOCK), 0, c->stream, d_descs, d_cmap,
-                               d_tcnt, d_stage, stage_stride, prim, d_pout, op);
-        } else if (op == OP_UNION) {
-            two_kernels = true;
-            HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-            launch_tiles<OP_UNION, MODE_WRITE>(c, d_descs, d_tpair, d_ta0,
-                                               total_tiles, nullptr, 0, d_tcnt,
-                                               d_toff, d_part);
-            HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-        } else {
-            u64 cblk = (total_tiles + 15) / 16;
-            hipLaunchKernelGGL(k_compact, dim3((u32)cblk), dim3(UA_BLOCK), 0,
-                               c->stream, d_descs, d_tpair, d_tb, d_tcnt, d_toff,
-                               d_part, d_stage, stage_stride, prim, total_tiles,
-                               op);
-            u64 sblk = (total_tiles + UA_BLOCK - 1) / UA_BLOCK;
-            hipLaunchKernelGGL(k_compact_small, dim3((u32)sblk), dim3(UA_BLOCK),
-                               0, c->stream, d_descs, d_tpair, d_tb, d_tcnt,
-                               d_toff, d_part, d_stage, stage_stride, prim,
-                               total_tiles, op);
-        }
-        if (!fused) {
-            u64 poutblk = ((u64)n_pairs + UA_BLOCK - 1) / UA_BLOCK;
-            hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0,
-                               c->stream, d_toff, d_part, d_tb, n_pairs, d_pout);
-        }
-        HIP_TRY(hipMemcpyAsync(out_lens, d_pout, (size_t)n_pairs * sizeof(u64),
+    enqueue_partition(p, c->stream);
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = enqueue_tiles(p, op, first_mode(op), nullptr, nullptr, c->stream))) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if (op != OP_MERGE_ALL) {
+        /* WS_POUT is reused between calls and zero-tile pairs get no fused
+         * chunk: their length must read 0 */
+        if (p.n_tchunks)
+            HIP_TRY(hipMemsetAsync(p.pout, 0, (size_t)n_pairs * sizeof(u64), c->stream));
+        if ((rc = enqueue_tail(c, p, op, nullptr, true, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(out_lens, p.pout, (size_t)n_pairs * sizeof(u64),
                                hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
 
-        /* stats: HIP-event time of the dominant (tile) kernel(s) */
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        c->kernel_ms += ms;
-        c->n_launches += 1;
-        if (two_kernels) {
-            float ms2 = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
-            c->kernel_ms += ms2;
-            c->n_launches += 1;
-        }
+    /* stats: HIP-event time of the dominant (tile) kernel(s) */
+    if ((rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
+    if (op == OP_UNION && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    if (op == OP_MERGE_ALL) {
+        /* duplicate-keeping merge: no scan / staging / compaction, lens are n+m */
+        for (int i = 0; i < n_pairs; i++) out_lens[i] = pairs[i].n + pairs[i].m;
+        c->bytes_algo += 2 * pl.in_bytes;
+        return UA_OK;
     }
     u64 out_elems = 0;
-    for (int p = 0; p < n_pairs; p++) out_elems += out_lens[p];
-    c->bytes_algo += in_bytes + 8 * out_elems;
+    for (int i = 0; i < n_pairs; i++) out_elems += out_lens[i];
+    c->bytes_algo += pl.in_bytes + 8 * out_elems;
     return UA_OK;
 }
 
@@ -1924,36 +1997,21 @@ extern "C" int ua_intersect_batch_dev(ua_ctx *c, const ua_dpair *pairs, int n_pa
 /* ==================== prepared batch (repeated-query path) ==================== */
 
 struct ua_batch {
-    int n_pairs = 0;
-    u64 total_tiles = 0;
+    /* view[0]: the batch's own buffers.  view[1]: the second set of the
+     * overlapped run_n (UA_OVERLAP: the aux tail of step i runs on the tail
+     * stream while step i+1's tile kernel fills the other set) — its own
+     * tcnt/toff/part/stage, no primary staging (prim == nullptr), the rest
+     * shared with view[0].  view[1].stage == nullptr until first needed.
+     * A view's n_tchunks == 0 means this batch keeps the scanned tail. */
+    UaPipe view[2];
     u64 in_bytes = 0;
-    u64 nchunks = 0;
-    void *mem = nullptr;     /* one allocation for all metadata arrays */
-    u64 *d_stage = nullptr;  /* lazy; stride UA_TILE (fits intersect + diff) */
-    u64 *d_stage_p = nullptr; /* lazy dense primary staging (UA_STAGE_P/tile) */
-    bool stage_p_tried = false; /* allocated (or failed) once: captured tail
-                                 * graphs freeze prim, so it must never change
-                                 * after the first staged run */
-    /* fused tail (k_tail_fused): chunk map built at create; n_tchunks == 0
-     * means this batch keeps the scanned tail (toggle off, or a pair over
-     * the chunk limit) */
-    UaTChunk *d_cmap = nullptr;
-    u64 n_tchunks = 0;
-    /* set-1 buffers for the overlapped run_n (aux tail of step i on the
-     * tail stream while step i+1's tile kernel fills the other set) */
-    u64 *d_stage1 = nullptr;
-    void *mem1 = nullptr; /* holds d_tcnt1 + d_toff1 + d_part1 */
-    u32 *d_tcnt1 = nullptr;
-    u64 *d_toff1 = nullptr;
-    u64 *d_part1 = nullptr;
-    UaDesc *d_descs = nullptr;
-    u64 *d_tb = nullptr;
-    u32 *d_tpair = nullptr;
-    u32 *d_ta0 = nullptr;
-    u32 *d_tcnt = nullptr;
-    u64 *d_toff = nullptr;
-    u64 *d_part = nullptr;
-    u64 *d_pout = nullptr;
+    void *mem = nullptr;  /* one allocation for view[0]'s metadata arrays */
+    void *mem1 = nullptr; /* view[1]'s tcnt + toff + part */
+    /* view[0].stage (stride UA_TILE: fits intersect + diff), view[0].prim and
+     * view[1].stage are separate lazy allocations owned by the batch.  prim
+     * is allocated (or fails) once: captured tail graphs freeze it, so it
+     * must never change after the first staged run */
+    bool stage_p_tried = false;
     /* cached per-thread merge-path splits (valid because the prepared
      * batch's inputs are immutable — same contract as the cached tile
      * partition): u16 per (tile, thread); written by the first run, read by
@@ -1967,40 +2025,15 @@ struct ua_batch {
     u64 *h_pout = nullptr;
 };
 
-extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
-                               ua_batch **out) {
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIP_TRY(hipSetDevice(c->device));
-    ua_batch *b = new ua_batch();
-    b->n_pairs = n_pairs;
-    std::vector<UaDesc> descs((size_t)std::max(n_pairs, 1));
-    std::vector<u64> tb((size_t)n_pairs + 1);
-    for (int p = 0; p < n_pairs; p++) {
-        const ua_dpair &pr = pairs[p];
-        if (pr.n >= (1ull << 31) || pr.m >= (1ull << 31)) {
-            delete b;
-            return UA_ERR_INVALID;
-        }
-        descs[p] = {pr.u, pr.n, pr.v, pr.m, pr.out, b->total_tiles};
-        tb[p] = b->total_tiles;
-        b->total_tiles += (pr.n + pr.m + UA_TILE - 1) / UA_TILE;
-        b->in_bytes += 8 * (pr.n + pr.m);
-    }
-    tb[n_pairs] = b->total_tiles;
-    u64 T = b->total_tiles;
-    b->nchunks = (T + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
-
-    std::vector<UaTChunk> cmap;
-    const bool fused = T > 0 && fused_tail_enabled() &&
-                       build_tail_chunks(tb, n_pairs, cmap);
-    if (!fused) cmap.clear();
-
-    size_t o_desc = 0;
-    size_t o_tb = align16(o_desc + descs.size() * sizeof(UaDesc));
-    size_t o_cmap = align16(o_tb + tb.size() * sizeof(u64));
-    size_t o_toff = align16(o_cmap + cmap.size() * sizeof(UaTChunk));
+/* allocate, upload and partition; on failure the caller destroys b */
+static int batch_init(ua_ctx *c, ua_batch *b, const UaPlan &pl, int n_pairs) {
+    UaPipe &p = b->view[0];
+    const u64 T = pl.T;
+    b->in_bytes = pl.in_bytes;
+    u64 nchunks = scan_chunks(T + 1);
+    size_t o_toff = align16(pl.head.size());
     size_t o_part = align16(o_toff + (T + 1) * sizeof(u64));
-    size_t o_pout = align16(o_part + (b->nchunks + 1) * sizeof(u64));
+    size_t o_pout = align16(o_part + (nchunks + 1) * sizeof(u64));
     size_t o_tpair = align16(o_pout + (size_t)std::max(n_pairs, 1) * sizeof(u64));
     size_t o_ta0 = align16(o_tpair + (T + 1) * sizeof(u32));
     size_t o_tcnt = align16(o_ta0 + (T + 1) * sizeof(u32));
@@ -2008,47 +2041,46 @@ extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
     hipError_t e = hipMalloc(&b->mem, total_bytes);
     if (e != hipSuccess) {
         g_last_hip = e;
-        delete b;
         return UA_ERR_NOMEM;
     }
     u8 *base = (u8 *)b->mem;
-    b->d_descs = (UaDesc *)(base + o_desc);
-    b->d_tb = (u64 *)(base + o_tb);
-    b->d_cmap = (UaTChunk *)(base + o_cmap);
-    b->n_tchunks = fused ? cmap.size() - 1 : 0;
-    b->d_toff = (u64 *)(base + o_toff);
-    b->d_part = (u64 *)(base + o_part);
-    b->d_pout = (u64 *)(base + o_pout);
-    b->d_tpair = (u32 *)(base + o_tpair);
-    b->d_ta0 = (u32 *)(base + o_ta0);
-    b->d_tcnt = (u32 *)(base + o_tcnt);
+    pipe_set_head(p, pl, n_pairs, base);
+    p.toff = (u64 *)(base + o_toff);
+    p.part = (u64 *)(base + o_part);
+    p.pout = (u64 *)(base + o_pout);
+    p.tpair = (u32 *)(base + o_tpair);
+    p.ta0 = (u32 *)(base + o_ta0);
+    p.tcnt = (u32 *)(base + o_tcnt);
 
-    /* descs, tb and the chunk map go up in one copy */
-    std::vector<u8> hostbuf(o_cmap + cmap.size() * sizeof(UaTChunk));
-    memcpy(hostbuf.data(), descs.data(), descs.size() * sizeof(UaDesc));
-    memcpy(hostbuf.data() + o_tb, tb.data(), tb.size() * sizeof(u64));
-    if (!cmap.empty())
-        memcpy(hostbuf.data() + o_cmap, cmap.data(), cmap.size() * sizeof(UaTChunk));
-    HIP_TRY(hipMemcpyAsync(b->mem, hostbuf.data(), hostbuf.size(),
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(b->d_tcnt + T, 0, sizeof(u32), c->stream));
-    HIP_TRY(hipMemsetAsync(b->d_toff, 0, sizeof(u64), c->stream));
-    HIP_TRY(hipMemsetAsync(b->d_part, 0, sizeof(u64), c->stream));
+    HIP_TRY(hipMemcpyAsync(b->mem, pl.head.data(), pl.head.size(), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemsetAsync(p.tcnt + T, 0, sizeof(u32), c->stream));
+    HIP_TRY(hipMemsetAsync(p.toff, 0, sizeof(u64), c->stream));
+    HIP_TRY(hipMemsetAsync(p.part, 0, sizeof(u64), c->stream));
     /* pout starts zeroed: zero-tile pairs get no fused-tail chunk, never
      * publish a length and stay 0 from here */
-    HIP_TRY(hipMemsetAsync(b->d_pout, 0,
-                           (size_t)std::max(n_pairs, 1) * sizeof(u64), c->stream));
-    if (T > 0) {
-        /* the partition depends only on the (immutable) pair contents:
-         * computed once here, reused every run */
-        u64 pblk = (T + UA_BLOCK - 1) / UA_BLOCK;
-        hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                           b->d_descs, b->d_tb, n_pairs, T, b->d_tpair, b->d_ta0, 0);
-        hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                           b->d_descs, b->d_tb, n_pairs, T, b->d_tpair, b->d_ta0, 1);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemsetAsync(p.pout, 0, (size_t)std::max(n_pairs, 1) * sizeof(u64),
+                           c->stream));
+    /* the partition depends only on the (immutable) pair contents:
+     * computed once here, reused every run */
+    if (T > 0) enqueue_partition(p, c->stream);
+    HIP_TRY(hipStreamSynchronize(c->stream)); /* pl.head is the caller's */
     HIP_TRY(hipGetLastError());
+    return UA_OK;
+}
+
+extern "C" int ua_batch_create(ua_ctx *c, const ua_dpair *pairs, int n_pairs,
+                               ua_batch **out) {
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    UaPlan pl;
+    int rc = plan_pairs(pairs, n_pairs, true, pl);
+    if (rc) return rc;
+    ua_batch *b = new ua_batch();
+    if ((rc = batch_init(c, b, pl, n_pairs))) {
+        ua_batch_destroy(c, b);
+        return rc;
+    }
     *out = b;
     return UA_OK;
 }
@@ -2062,9 +2094,9 @@ extern "C" void ua_batch_destroy(ua_ctx *c, ua_batch *b) {
     if (b->h_pout) (void)hipHostFree(b->h_pout);
     if (b->mem) (void)hipFree(b->mem);
     if (b->mem1) (void)hipFree(b->mem1);
-    if (b->d_stage) (void)hipFree(b->d_stage);
-    if (b->d_stage_p) (void)hipFree(b->d_stage_p);
-    if (b->d_stage1) (void)hipFree(b->d_stage1);
+    if (b->view[0].stage) (void)hipFree(b->view[0].stage);
+    if (b->view[0].prim) (void)hipFree((void *)b->view[0].prim);
+    if (b->view[1].stage) (void)hipFree(b->view[1].stage);
     if (b->d_isplit) (void)hipFree(b->d_isplit);
     delete b;
 }
@@ -2085,7 +2117,7 @@ static void batch_isplit(ua_batch *b, const u32 **isin, u32 **isout) {
     *isin = nullptr;
     *isout = nullptr;
     if (!b->d_isplit) {
-        size_t bytes = (size_t)b->total_tiles * UA_TBLOCK * sizeof(u32);
+        size_t bytes = (size_t)b->view[0].T * UA_TBLOCK * sizeof(u32);
         if (bytes == 0 || hipMalloc((void **)&b->d_isplit, bytes) != hipSuccess) {
             b->d_isplit = nullptr; /* cacheless fallback */
             (void)hipGetLastError();
@@ -2099,103 +2131,26 @@ static void batch_isplit(ua_batch *b, const u32 **isin, u32 **isout) {
     }
 }
 
-/* the staged TILE kernel (eager, event-timed) */
-static int batch_tiles_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
-                           bool record_events, int set) {
-    u64 T = b->total_tiles;
-    u64 *stage = set ? b->d_stage1 : b->d_stage;
-    u32 *tcnt = set ? b->d_tcnt1 : b->d_tcnt;
+/* the first tile pass of one run (eager; event-timed on the sampled pass) */
+static int batch_tiles(ua_ctx *c, ua_batch *b, int kop, bool timed, int set) {
     const u32 *isin;
     u32 *isout;
     batch_isplit(b, &isin, &isout);
-    if (record_events) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    /* dense primary staging rides the (otherwise unused) offs arg of the
-     * STAGE launch; only for set 0 (overlap keeps the overflow-only layout).
-     * One allocation attempt per batch: a failure is recorded, not retried,
-     * so prim is the same on every run and in every captured tail. */
-    const u64 *prim = nullptr;
-    if (set == 0 && kop != OP_UNION) {
-        if (!b->stage_p_tried) {
-            b->stage_p_tried = true;
-            size_t pbytes = (size_t)(T ? T : 1) * UA_STAGE_P * sizeof(u64);
-            if (hipMalloc((void **)&b->d_stage_p, pbytes) != hipSuccess) {
-                b->d_stage_p = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        prim = b->d_stage_p;
-    }
-    if (kop == OP_INTERSECT) {
-        launch_tiles<OP_INTERSECT, MODE_STAGE>(c, b->d_descs, b->d_tpair, b->d_ta0,
-                                               T, stage, stride, tcnt,
-                                               prim, nullptr, isin, isout);
-    } else if (kop == OP_DIFF) {
-        launch_tiles<OP_DIFF, MODE_STAGE>(c, b->d_descs, b->d_tpair, b->d_ta0, T,
-                                          stage, stride, tcnt, prim,
-                                          nullptr, isin, isout);
-    } else {
-        launch_tiles<OP_UNION, MODE_COUNT>(c, b->d_descs, b->d_tpair, b->d_ta0, T,
-                                           nullptr, 0, b->d_tcnt, nullptr, nullptr,
-                                           isin, isout);
-    }
-    if (record_events) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    return UA_OK;
-}
-
-/* the aux tail, leaving the pair lengths in d_pout (the caller copies them
- * to the host once, after the last pass).  Intersect/diff within the chunk
- * limit: ONE k_tail_fused.  Otherwise scan + write/compact + pair_out.
- * Captured into a hipGraph for intersect/diff; union's WRITE pass is a
- * second tile kernel that needs live events, so union stays eager
- * throughout. */
-static int batch_tail_seq(ua_ctx *c, ua_batch *b, int kop, u64 stride,
-                          bool record_events, int set, hipStream_t st) {
-    /* set 1 (overlap) has no primary region: prim == nullptr */
-    const u64 *prim = (set == 0) ? b->d_stage_p : nullptr;
-    if (kop != OP_UNION && b->n_tchunks > 0) {
-        hipLaunchKernelGGL(k_tail_fused, dim3((u32)b->n_tchunks), dim3(UA_BLOCK), 0,
-                           st, b->d_descs, b->d_cmap, set ? b->d_tcnt1 : b->d_tcnt,
-                           set ? b->d_stage1 : b->d_stage, stride, prim, b->d_pout,
-                           kop);
-        return UA_OK;
-    }
-    u64 T = b->total_tiles;
-    u64 nch = b->nchunks;
-    u32 *tcnt = set ? b->d_tcnt1 : b->d_tcnt;
-    u64 *toff = set ? b->d_toff1 : b->d_toff;
-    u64 *part = set ? b->d_part1 : b->d_part;
-    u64 *stage = set ? b->d_stage1 : b->d_stage;
-    hipLaunchKernelGGL(k_scan1, dim3((u32)nch), dim3(UA_BLOCK), 0, st,
-                       tcnt, T + 1, toff, part);
-    hipLaunchKernelGGL(k_scan2, dim3(1), dim3(UA_BLOCK), 0, st, part,
-                       nch);
-    if (kop == OP_UNION) {
-        /* the count pass of this same run already stored the splits */
-        const u32 *isw = (b->i0_ready && b->d_isplit) ? b->d_isplit : nullptr;
-        if (record_events) HIP_TRY(hipEventRecord(c->ev[2], st));
-        launch_tiles<OP_UNION, MODE_WRITE>(c, b->d_descs, b->d_tpair, b->d_ta0, T,
-                                           nullptr, 0, b->d_tcnt, b->d_toff,
-                                           b->d_part, isw, nullptr);
-        if (record_events) HIP_TRY(hipEventRecord(c->ev[3], st));
-    } else {
-        hipLaunchKernelGGL(k_compact, dim3((u32)((T + 15) / 16)), dim3(UA_BLOCK), 0,
-                           st, b->d_descs, b->d_tpair, b->d_tb, tcnt, toff,
-                           part, stage, stride, prim, T, kop);
-        hipLaunchKernelGGL(k_compact_small, dim3((u32)((T + UA_BLOCK - 1) / UA_BLOCK)),
-                           dim3(UA_BLOCK), 0, st, b->d_descs, b->d_tpair, b->d_tb, tcnt,
-                           toff, part, stage, stride, prim, T, kop);
-    }
-    u64 poutblk = ((u64)b->n_pairs + UA_BLOCK - 1) / UA_BLOCK;
-    hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, st,
-                       toff, part, b->d_tb, b->n_pairs, b->d_pout);
+    if (timed) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    int rc = enqueue_tiles(b->view[set], kop, first_mode(kop), isin, isout, c->stream);
+    if (rc) return rc;
+    if (timed) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     return UA_OK;
 }
 
 /* one tail dispatch: graph replay when available, else eager enqueue.
  * Returns UA_OK with the tail enqueued (or already executed, for the one
  * capture-validation run). */
-static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
-                               bool record_events, int set, hipStream_t st) {
+static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, bool timed, int set,
+                               hipStream_t st) {
+    const UaPipe &p = b->view[set];
+    /* union's WRITE pass reuses the splits its count pass just stored */
+    const u32 *isw = b->i0_ready ? b->d_isplit : nullptr;
 #if UA_GRAPH
     if (getenv("UA_NO_TAILGRAPH")) b->no_graph = true;
     if (kop != OP_UNION) { /* union's tail holds an event-timed kernel */
@@ -2207,7 +2162,7 @@ static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
             hipError_t ce = hipStreamBeginCapture(st,
                                                   hipStreamCaptureModeThreadLocal);
             if (ce == hipSuccess) {
-                int rc = batch_tail_seq(c, b, kop, stride, false, set, st);
+                int rc = enqueue_tail(c, p, kop, isw, false, st);
                 hipGraph_t gr = nullptr;
                 hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == UA_OK && ee == hipSuccess && gr) {
@@ -2253,7 +2208,32 @@ static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
         }
     }
 #endif
-    return batch_tail_seq(c, b, kop, stride, record_events, set, st);
+    return enqueue_tail(c, p, kop, isw, timed, st);
+}
+
+/* UA_OVERLAP's second buffer set, allocated on first use; false = no memory
+ * (the caller stays serial) */
+static bool batch_alloc_set1(ua_batch *b) {
+    const UaPipe &v0 = b->view[0];
+    size_t o_cnt1 = 0;
+    size_t o_off1 = align16(o_cnt1 + (v0.T + 1) * sizeof(u32));
+    size_t o_part1 = align16(o_off1 + (v0.T + 1) * sizeof(u64));
+    size_t tot1 = align16(o_part1 + (v0.nchunks + 1) * sizeof(u64));
+    u64 *stage1 = nullptr;
+    hipError_t e = hipMalloc(&b->mem1, tot1);
+    if (e == hipSuccess) e = hipMalloc((void **)&stage1, v0.T * UA_TILE * sizeof(u64));
+    if (e != hipSuccess) {
+        if (b->mem1) { (void)hipFree(b->mem1); b->mem1 = nullptr; }
+        return false;
+    }
+    u8 *m1 = (u8 *)b->mem1;
+    b->view[1] = v0;
+    b->view[1].tcnt = (u32 *)(m1 + o_cnt1);
+    b->view[1].toff = (u64 *)(m1 + o_off1);
+    b->view[1].part = (u64 *)(m1 + o_part1);
+    b->view[1].stage = stage1;
+    b->view[1].prim = nullptr;
+    return true;
 }
 
 /* n_runs passes of one op over the prepared batch, enqueued back-to-back
@@ -2263,31 +2243,41 @@ static int batch_tail_dispatch(ua_ctx *c, ua_batch *b, int kop, u64 stride,
 static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
                             uint64_t *out_lens) {
     HIP_TRY(hipSetDevice(c->device));
-    if (b->n_pairs == 0 || n_runs <= 0) return UA_OK;
+    UaPipe &v0 = b->view[0];
+    const int n_pairs = v0.n_pairs;
+    if (n_pairs == 0 || n_runs <= 0) return UA_OK;
     int kop = (op == UA_OP_INTERSECT) ? OP_INTERSECT
               : (op == UA_OP_MERGE) ? OP_UNION
               : (op == UA_OP_DIFFERENCE) ? OP_DIFF
                                          : -1;
     if (kop < 0) return UA_ERR_INVALID;
-    u64 T = b->total_tiles;
+    const u64 T = v0.T;
     if (T == 0) {
-        for (int p = 0; p < b->n_pairs; p++) out_lens[p] = 0;
+        for (int p = 0; p < n_pairs; p++) out_lens[p] = 0;
         return UA_OK;
     }
-    const bool two_kernels = (kop == OP_UNION);
     int rc;
-    u64 stride = (kop == OP_INTERSECT) ? UA_TILE / 2 : UA_TILE;
-    if (kop != OP_UNION && !b->d_stage) {
-        hipError_t e = hipMalloc((void **)&b->d_stage,
-                                 (T ? T : 1) * UA_TILE * sizeof(u64));
+    if (kop != OP_UNION && !v0.stage) {
+        hipError_t e = hipMalloc((void **)&v0.stage, T * UA_TILE * sizeof(u64));
         if (e != hipSuccess) {
             g_last_hip = e;
             return UA_ERR_NOMEM;
         }
     }
+    /* dense primary staging, view[0] only.  One allocation attempt per
+     * batch: a failure is recorded, not retried, so prim is the same on
+     * every run and in every captured tail. */
+    if (kop != OP_UNION && !b->stage_p_tried) {
+        b->stage_p_tried = true;
+        u64 *prim = nullptr;
+        if (hipMalloc((void **)&prim, (size_t)T * UA_STAGE_P * sizeof(u64)) != hipSuccess) {
+            prim = nullptr;
+            (void)hipGetLastError();
+        }
+        v0.prim = prim;
+    }
     if (!b->h_pout) {
-        hipError_t e = hipHostMalloc((void **)&b->h_pout,
-                                     (size_t)b->n_pairs * sizeof(u64));
+        hipError_t e = hipHostMalloc((void **)&b->h_pout, (size_t)n_pairs * sizeof(u64));
         if (e != hipSuccess) {
             g_last_hip = e;
             return UA_ERR_NOMEM;
@@ -2307,77 +2297,37 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
     bool ovl = (kop != OP_UNION) && n_runs > 1 && c->stream_tail &&
                ovl_env && ovl_env[0] == '1';
     if (ovl && !b->mem1) {
-        size_t o_cnt1 = 0;
-        size_t o_off1 = align16(o_cnt1 + (T + 1) * sizeof(u32));
-        size_t o_part1 = align16(o_off1 + (T + 1) * sizeof(u64));
-        size_t tot1 = align16(o_part1 + (b->nchunks + 1) * sizeof(u64));
-        hipError_t e = hipMalloc(&b->mem1, tot1);
-        if (e == hipSuccess)
-            e = hipMalloc((void **)&b->d_stage1,
-                          (T ? T : 1) * UA_TILE * sizeof(u64));
-        if (e != hipSuccess) {
-            if (b->mem1) { (void)hipFree(b->mem1); b->mem1 = nullptr; }
-            ovl = false; /* fall back to the serial path */
-        } else {
-            u8 *m1 = (u8 *)b->mem1;
-            b->d_tcnt1 = (u32 *)(m1 + o_cnt1);
-            b->d_toff1 = (u64 *)(m1 + o_off1);
-            b->d_part1 = (u64 *)(m1 + o_part1);
-            HIP_TRY(hipMemsetAsync(b->d_tcnt1 + T, 0, sizeof(u32), c->stream));
-        }
-    } else if (ovl && !b->d_stage1) {
-        ovl = false;
+        ovl = batch_alloc_set1(b);
+        if (ovl)
+            HIP_TRY(hipMemsetAsync(b->view[1].tcnt + T, 0, sizeof(u32), c->stream));
     }
-    if (ovl) {
-        for (int it = 0; it < n_runs; it++) {
-            bool rec = (it == n_runs - 1);
-            int s = it & 1;
-            /* set s's tail from run it-2 must be done before refilling */
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->oev[2 + s], 0));
-            if ((rc = batch_tiles_seq(c, b, kop, stride, rec, s))) return rc;
+    hipStream_t tail_st = ovl ? c->stream_tail : c->stream;
+    for (int it = 0; it < n_runs; it++) {
+        bool timed = (it == n_runs - 1);
+        int s = ovl ? (it & 1) : 0;
+        /* set s's tail from run it-2 must be done before refilling */
+        if (ovl) HIP_TRY(hipStreamWaitEvent(c->stream, c->oev[2 + s], 0));
+        if ((rc = batch_tiles(c, b, kop, timed, s))) return rc;
+        if (ovl) {
             HIP_TRY(hipEventRecord(c->oev[s], c->stream));
-            HIP_TRY(hipStreamWaitEvent(c->stream_tail, c->oev[s], 0));
-            if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, s,
-                                          c->stream_tail)))
-                return rc;
-            HIP_TRY(hipEventRecord(c->oev[2 + s], c->stream_tail));
+            HIP_TRY(hipStreamWaitEvent(tail_st, c->oev[s], 0));
         }
-        /* lengths: one copy after the last pass (only the last pass's
-         * are returned); tails are serialized on the tail stream */
-        HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
-                               (size_t)b->n_pairs * sizeof(u64),
-                               hipMemcpyDeviceToHost, c->stream_tail));
-        HIP_TRY(hipStreamSynchronize(c->stream_tail));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    } else {
-        for (int it = 0; it < n_runs; it++) {
-            bool rec = (it == n_runs - 1);
-            if ((rc = batch_tiles_seq(c, b, kop, stride, rec, 0))) return rc;
-            if ((rc = batch_tail_dispatch(c, b, kop, stride, rec, 0, c->stream)))
-                return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(b->h_pout, b->d_pout,
-                               (size_t)b->n_pairs * sizeof(u64),
-                               hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((rc = batch_tail_dispatch(c, b, kop, timed, s, tail_st))) return rc;
+        if (ovl) HIP_TRY(hipEventRecord(c->oev[2 + s], tail_st));
     }
+    /* lengths: one copy after the last pass (only the last pass's are
+     * returned); tails are serialized on their stream */
+    HIP_TRY(hipMemcpyAsync(b->h_pout, v0.pout, (size_t)n_pairs * sizeof(u64),
+                           hipMemcpyDeviceToHost, tail_st));
+    HIP_TRY(hipStreamSynchronize(tail_st));
+    if (ovl) HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
-    memcpy(out_lens, b->h_pout, (size_t)b->n_pairs * sizeof(u64));
+    memcpy(out_lens, b->h_pout, (size_t)n_pairs * sizeof(u64));
 
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) {
-        c->kernel_ms += ms;
-        c->n_launches += 1;
-    }
-    if (two_kernels) {
-        float ms2 = 0.f;
-        if (hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]) == hipSuccess) {
-            c->kernel_ms += ms2;
-            c->n_launches += 1;
-        }
-    }
+    if ((rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
+    if (kop == OP_UNION && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
     u64 out_elems = 0;
-    for (int p = 0; p < b->n_pairs; p++) out_elems += out_lens[p];
+    for (int p = 0; p < n_pairs; p++) out_elems += out_lens[p];
     c->bytes_algo += ((u64)n_runs) * b->in_bytes + ((u64)n_runs) * 8 * out_elems;
     return UA_OK;
 }
@@ -2531,12 +2481,7 @@ extern "C" int ua_apply_filter_batch_dev(ua_ctx *c, const ua_dfilter *tasks,
         if (tasks[p].n == 0) out_lens[p] = 0; /* no tiles -> never published */
         out_elems += out_lens[p];
     }
-    if (T > 0) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        c->kernel_ms += ms;
-        c->n_launches += 1;
-    }
+    if (T > 0 && (rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
     c->bytes_algo += in_bytes + 8 * out_elems;
     return UA_OK;
 }
@@ -2588,12 +2533,11 @@ extern "C" int ua_intersect_k_dev(ua_ctx *c, const uint64_t *const *lists,
         *out_n = 0;
         return UA_OK;
     }
+    HIP_TRY(hipSetDevice(c->device));
     std::vector<int> ord(k);
     for (int i = 0; i < k; i++) ord[i] = i;
     std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return lens[a] < lens[b]; });
     if (k == 1) {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipMemcpyAsync(out, lists[0], lens[0] * sizeof(u64),
                                hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2602,20 +2546,15 @@ extern "C" int ua_intersect_k_dev(ua_ctx *c, const uint64_t *const *lists,
     }
     u64 cap = lens[ord[0]];
     int rc;
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        if ((rc = ws_reserve(c, WS_SCRATCH_A, (cap ? cap : 1) * sizeof(u64)))) return rc;
-    }
+    if ((rc = ws_reserve(c, WS_SCRATCH_A, (cap ? cap : 1) * sizeof(u64)))) return rc;
     u64 *scratch = (u64 *)c->ws[WS_SCRATCH_A];
     ua_dpair pr;
     u64 len0 = 0;
     pr = {lists[ord[0]], lens[ord[0]], lists[ord[1]], lens[ord[1]], out};
-    if ((rc = run_batch(c, &pr, 1, &len0, OP_INTERSECT))) return rc;
+    if ((rc = run_batch_locked(c, &pr, 1, &len0, OP_INTERSECT))) return rc;
     for (int j = 2; j < k && len0 > 0; j++) {
         pr = {out, len0, lists[ord[j]], lens[ord[j]], scratch};
-        if ((rc = run_batch(c, &pr, 1, &len0, OP_INTERSECT))) return rc;
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = run_batch_locked(c, &pr, 1, &len0, OP_INTERSECT))) return rc;
         HIP_TRY(hipMemcpyAsync(out, scratch, len0 * sizeof(u64),
                                hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2728,47 +2667,37 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     if ((rc = ws_reserve(c, WS_TA0, (max_tiles + 1) * sizeof(u32)))) return rc;
     if ((rc = ws_reserve(c, WS_TCNT, (max_tiles + 1) * sizeof(u32)))) return rc;
     if ((rc = ws_reserve(c, WS_TOFF, (max_tiles + 1) * sizeof(u64)))) return rc;
-    u64 max_chunks = (max_tiles + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
-    if ((rc = ws_reserve(c, WS_PARTIAL, (max_chunks + 1) * sizeof(u64)))) return rc;
-    u32 *d_tpair = (u32 *)c->ws[WS_TPAIR];
-    u32 *d_ta0 = (u32 *)c->ws[WS_TA0];
-    u32 *d_tcnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_toff = (u64 *)c->ws[WS_TOFF];
-    u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
+    if ((rc = ws_reserve(c, WS_PARTIAL, (scan_chunks(max_tiles + 1) + 1) * sizeof(u64))))
+        return rc;
+    /* one view per round: the round's slice of the concatenated uploads
+     * over the shared tile slots; a round's pout is the next round's lens */
+    UaPipe p;
+    p.tpair = (u32 *)c->ws[WS_TPAIR];
+    p.ta0 = (u32 *)c->ws[WS_TA0];
+    p.tcnt = (u32 *)c->ws[WS_TCNT];
+    p.toff = (u64 *)c->ws[WS_TOFF];
+    p.part = (u64 *)c->ws[WS_PARTIAL];
 
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     int lcur = 0;
     for (int r = 0; r < R; r++) {
         const Round &rd = rounds[r];
-        UaDesc *d_descs = d_descs_all + rd.desc_off;
-        u64 *d_tb = d_tb_all + rd.tb_off;
-        u64 T = rd.total_tiles;
+        p.descs = d_descs_all + rd.desc_off;
+        p.tb = d_tb_all + rd.tb_off;
+        p.n_pairs = rd.npair;
+        p.T = rd.total_tiles;
+        p.nchunks = scan_chunks(p.T + 1);
+        p.pout = d_lens[lcur ^ 1];
         u64 mk = ((u64)rd.npair + UA_BLOCK - 1) / UA_BLOCK;
         hipLaunchKernelGGL(k_make_descs, dim3((u32)mk), dim3(UA_BLOCK), 0, c->stream,
-                           d_descs, d_lens[lcur], rd.nk_prev, rd.npair);
-        HIP_TRY(hipMemsetAsync(d_tcnt + T, 0, sizeof(u32), c->stream));
-        if (T > 0) {
-            u64 pblk = (T + UA_BLOCK - 1) / UA_BLOCK;
-            hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                               d_descs, d_tb, rd.npair, T, d_tpair, d_ta0, 0);
-            hipLaunchKernelGGL(k_partition, dim3((u32)pblk), dim3(UA_BLOCK), 0, c->stream,
-                               d_descs, d_tb, rd.npair, T, d_tpair, d_ta0, 1);
-            launch_tiles<OP_UNION, MODE_COUNT>(c, d_descs, d_tpair, d_ta0, T, nullptr,
-                                               0, d_tcnt, nullptr, nullptr);
-            u64 nchunks = (T + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
-            hipLaunchKernelGGL(k_scan1, dim3((u32)nchunks), dim3(UA_BLOCK), 0, c->stream,
-                               d_tcnt, T + 1, d_toff, d_part);
-            hipLaunchKernelGGL(k_scan2, dim3(1), dim3(UA_BLOCK), 0, c->stream, d_part,
-                               nchunks);
-            launch_tiles<OP_UNION, MODE_WRITE>(c, d_descs, d_tpair, d_ta0, T, nullptr,
-                                               0, d_tcnt, d_toff, d_part);
-        } else {
-            HIP_TRY(hipMemsetAsync(d_toff, 0, sizeof(u64), c->stream));
-            HIP_TRY(hipMemsetAsync(d_part, 0, sizeof(u64), c->stream));
+                           p.descs, d_lens[lcur], rd.nk_prev, rd.npair);
+        HIP_TRY(hipMemsetAsync(p.tcnt + p.T, 0, sizeof(u32), c->stream));
+        if (p.T > 0) {
+            enqueue_partition(p, c->stream);
+            if ((rc = enqueue_tiles(p, OP_UNION, MODE_COUNT, nullptr, nullptr, c->stream)))
+                return rc;
         }
-        u64 poutblk = ((u64)rd.npair + UA_BLOCK - 1) / UA_BLOCK;
-        hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, c->stream,
-                           d_toff, d_part, d_tb, rd.npair, d_lens[lcur ^ 1]);
+        if ((rc = enqueue_tail(c, p, OP_UNION, nullptr, false, c->stream))) return rc;
         lcur ^= 1;
     }
     /* final item: data in ptrs[0] (capacity position), length in d_lens[lcur][0] */
@@ -2781,12 +2710,9 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
-    float ms = 0.f;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->kernel_ms += ms;
-    c->n_launches += 2 * R;
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], 2 * R))) return rc;
     c->bytes_algo += 8 * 3 * cap_work; /* capacity upper bound (union count+write) */
     *out_n = final_len;
     return UA_OK;
@@ -2867,7 +2793,7 @@ static int run_packed_locked(ua_ctx *c, const ua_dpack *pk, u64 after, const u64
     }
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
 
-    if ((rc = run_scan(c, d_cnt, nb + 1, d_off))) return rc;
+    if ((rc = ws_scan(c, d_cnt, nb + 1, d_off))) return rc;
     u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
     hipLaunchKernelGGL(k_compact_flat, dim3((u32)((nb + 15) / 16)), dim3(UA_BLOCK), 0,
                        c->stream, out, d_cnt, d_off, d_part, d_stage,
@@ -2881,10 +2807,7 @@ static int run_packed_locked(ua_ctx *c, const ua_dpack *pk, u64 after, const u64
     HIP_TRY(hipGetLastError());
     *out_n = off_nb + part_nb;
 
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->kernel_ms += ms;
-    c->n_launches += 1;
+    if ((rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
     /* algorithmic bytes: deltas + block headers + 8*(m + out) */
     u64 hdr = nb * (8 + 4 + 8);
     u64 dbytes = 0;
@@ -2907,6 +2830,70 @@ extern "C" int ua_intersect_packed_dev(ua_ctx *c, const ua_dpack *pk, uint64_t a
 }
 
 /* ---- multi-pack fan-out: one grid over every pack's blocks ---- */
+
+/* one fan-out instance as the kernels see it (owns nothing): filled from the
+ * ctx workspace by the one-shot call and from ua_pbatch's allocation */
+struct UaFan {
+    const u64 *bases = nullptr;
+    const u32 *nums = nullptr;
+    const u64 *doffs = nullptr;
+    const u8 *deltas = nullptr;
+    u64 nb = 0;               /* blocks over all packs */
+    const u64 *pbb = nullptr; /* per-pack first block, n_packs + 1 */
+    const ua_ptask *tasks = nullptr;
+    int n_packs = 0;
+    u32 *cnt = nullptr;       /* nb + 1 counts; the owner zeroes [nb] */
+    u64 *offs = nullptr;
+    u64 *part = nullptr;
+    u64 nchunks = 0;          /* scan chunks over the nb + 1 counts */
+    u64 *stage = nullptr;
+    u64 *pout = nullptr;
+};
+
+/* k_packed -> scan -> k_compact_pack -> k_pair_out on the ctx stream */
+static int enqueue_packed_fanout(ua_ctx *c, const UaFan &f) {
+    if (f.nb > 0) {
+        u64 nwg = (f.nb + UA_PKW - 1) / UA_PKW;
+        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+        hipLaunchKernelGGL(k_packed<0>, dim3((u32)nwg), dim3(UA_BLOCK), 0, c->stream,
+                           f.bases, f.nums, f.doffs, f.deltas, f.nb, (u64)0,
+                           (const u64 *)nullptr, (u64)0, f.stage, f.cnt, f.pbb, f.n_packs,
+                           f.tasks);
+        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    }
+    enqueue_scan(f.cnt, f.nb + 1, f.offs, f.part, f.nchunks, c->stream);
+    if (f.nb > 0)
+        hipLaunchKernelGGL(k_compact_pack, dim3((u32)((f.nb + 15) / 16)), dim3(UA_BLOCK),
+                           0, c->stream, f.tasks, f.pbb, f.n_packs, f.cnt, f.offs, f.part,
+                           f.stage, f.nb);
+    u64 poutblk = ((u64)f.n_packs + UA_BLOCK - 1) / UA_BLOCK;
+    hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, c->stream,
+                       f.offs, f.part, f.pbb, f.n_packs, f.pout);
+    return UA_OK;
+}
+
+/* the fan-out's lengths to the host, and the call's one sync */
+static int packed_fanout_lens(ua_ctx *c, const UaFan &f, uint64_t *out_lens) {
+    HIP_TRY(hipMemcpyAsync(out_lens, f.pout, (size_t)f.n_packs * sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    return UA_OK;
+}
+
+/* algorithmic bytes: deltas + block headers + 8*(m + out) */
+static int packed_fanout_stats(ua_ctx *c, const UaFan &f, const uint64_t *out_lens,
+                               u64 deltas_bytes, u64 sum_m) {
+    if (f.nb > 0) {
+        int rc = stats_add(c, c->ev[0], c->ev[1]);
+        if (rc) return rc;
+    }
+    u64 out_elems = 0;
+    for (int p = 0; p < f.n_packs; p++) out_elems += out_lens[p];
+    c->bytes_algo += deltas_bytes + f.nb * 20 + 8 * (sum_m + out_elems);
+    return UA_OK;
+}
+
 extern "C" int ua_intersect_packed_batch_dev(ua_ctx *c, const uint64_t *bases,
                                              const uint32_t *num_uids,
                                              const uint64_t *delta_offs,
@@ -2917,76 +2904,53 @@ extern "C" int ua_intersect_packed_batch_dev(ua_ctx *c, const uint64_t *bases,
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     if (n_packs <= 0) return UA_OK;
-    u64 nb = pack_block_base[n_packs];
+    UaFan f;
+    f.bases = bases;
+    f.nums = num_uids;
+    f.doffs = delta_offs;
+    f.deltas = deltas;
+    f.n_packs = n_packs;
+    f.nb = pack_block_base[n_packs];
+    f.nchunks = scan_chunks(f.nb + 1);
+    const u64 nb = f.nb;
     int rc;
     /* upload pbb + tasks in one copy (WS_DESC is free during this call) */
     size_t pbb_bytes = ((size_t)n_packs + 1) * sizeof(u64);
     size_t task_bytes = (size_t)n_packs * sizeof(ua_ptask);
     if ((rc = ws_reserve(c, WS_DESC, pbb_bytes + task_bytes))) return rc;
-    u64 *d_pbb = (u64 *)c->ws[WS_DESC];
-    ua_ptask *d_tasks = (ua_ptask *)((u8 *)c->ws[WS_DESC] + pbb_bytes);
+    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_PARTIAL, (f.nchunks + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_STAGE, (nb ? nb : 1) * UA_MAX_BLOCK_UIDS * sizeof(u64))))
+        return rc;
+    if ((rc = ws_reserve(c, WS_POUT, (size_t)n_packs * sizeof(u64)))) return rc;
+    f.pbb = (const u64 *)c->ws[WS_DESC];
+    f.tasks = (const ua_ptask *)((u8 *)c->ws[WS_DESC] + pbb_bytes);
+    f.cnt = (u32 *)c->ws[WS_TCNT];
+    f.offs = (u64 *)c->ws[WS_TOFF];
+    f.part = (u64 *)c->ws[WS_PARTIAL];
+    f.stage = (u64 *)c->ws[WS_STAGE];
+    f.pout = (u64 *)c->ws[WS_POUT];
+
     std::vector<u8> hostbuf(pbb_bytes + task_bytes);
     memcpy(hostbuf.data(), pack_block_base, pbb_bytes);
     memcpy(hostbuf.data() + pbb_bytes, tasks, task_bytes);
     HIP_TRY(hipMemcpyAsync(c->ws[WS_DESC], hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
-
-    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
-    if ((rc = ws_reserve(c, WS_STAGE, (nb ? nb : 1) * UA_MAX_BLOCK_UIDS * sizeof(u64))))
-        return rc;
-    if ((rc = ws_reserve(c, WS_POUT, (size_t)n_packs * sizeof(u64)))) return rc;
-    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_off_arr = (u64 *)c->ws[WS_TOFF];
-    u64 *d_stage = (u64 *)c->ws[WS_STAGE];
-    u64 *d_pout = (u64 *)c->ws[WS_POUT];
-    HIP_TRY(hipMemsetAsync(d_cnt + nb, 0, sizeof(u32), c->stream));
-
-    if (nb > 0) {
-        if ((rc = pack_validate_begin(c, num_uids, delta_offs, nb))) return rc;
-        u64 nwg = (nb + UA_PKW - 1) / UA_PKW;
-        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        hipLaunchKernelGGL(k_packed<0>, dim3((u32)nwg), dim3(UA_BLOCK), 0, c->stream,
-                           bases, num_uids, delta_offs, deltas, nb, (u64)0,
-                           (const u64 *)nullptr, (u64)0, d_stage, d_cnt, d_pbb,
-                           n_packs, d_tasks);
-        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    }
-    if ((rc = run_scan(c, d_cnt, nb + 1, d_off_arr))) return rc;
-    u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
-    if (nb > 0) {
-        hipLaunchKernelGGL(k_compact_pack, dim3((u32)((nb + 15) / 16)), dim3(UA_BLOCK),
-                           0, c->stream, d_tasks, d_pbb, n_packs, d_cnt, d_off_arr,
-                           d_part, d_stage, nb);
-    }
-    u64 poutblk = ((u64)n_packs + UA_BLOCK - 1) / UA_BLOCK;
-    hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, c->stream,
-                       d_off_arr, d_part, d_pbb, n_packs, d_pout);
-    HIP_TRY(hipMemcpyAsync(out_lens, d_pout, (size_t)n_packs * sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(f.cnt + nb, 0, sizeof(u32), c->stream));
+    if (nb > 0 && (rc = pack_validate_begin(c, num_uids, delta_offs, nb))) return rc;
+    if ((rc = enqueue_packed_fanout(c, f))) return rc;
     u64 dbytes = 0;
-    HIP_TRY(hipMemcpyAsync(&dbytes, delta_offs + nb, sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&dbytes, delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    if ((rc = packed_fanout_lens(c, f, out_lens))) return rc;
     if (nb > 0 && (rc = pack_validate_end(c))) {
         for (int p = 0; p < n_packs; p++) out_lens[p] = 0;
         return rc;
     }
-
-    if (nb > 0) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        c->kernel_ms += ms;
-        c->n_launches += 1;
-    }
-    u64 out_elems = 0, m_elems = 0;
-    for (int p = 0; p < n_packs; p++) {
-        out_elems += out_lens[p];
-        m_elems += tasks[p].m;
-    }
-    c->bytes_algo += dbytes + nb * 20 + 8 * (m_elems + out_elems);
-    return UA_OK;
+    u64 m_elems = 0;
+    for (int p = 0; p < n_packs; p++) m_elems += tasks[p].m;
+    return packed_fanout_stats(c, f, out_lens, dbytes, m_elems);
 }
 
 extern "C" int ua_decode_dev(ua_ctx *c, const ua_dpack *pk, uint64_t seek_uid, uint64_t *out,
@@ -2998,23 +2962,10 @@ extern "C" int ua_decode_dev(ua_ctx *c, const ua_dpack *pk, uint64_t seek_uid, u
 /* ---- prepared pack fan-out (standing query plan) ---- */
 
 struct ua_pbatch {
-    int n_packs = 0;
-    u64 nb = 0;
+    UaFan fan; /* over mem: pbb + tasks + cnt + offs + partials + pout + staging */
+    void *mem = nullptr;
     u64 deltas_bytes = 0;
     u64 sum_m = 0;
-    const u64 *bases = nullptr;
-    const u32 *nums = nullptr;
-    const u64 *doffs = nullptr;
-    const u8 *deltas = nullptr;
-    void *mem = nullptr; /* pbb + tasks + cnt + offs + partials + pout + staging */
-    u64 *d_pbb = nullptr;
-    ua_ptask *d_tasks = nullptr;
-    u32 *d_cnt = nullptr;
-    u64 *d_offs = nullptr;
-    u64 *d_part = nullptr;
-    u64 *d_pout = nullptr;
-    u64 *d_stage = nullptr;
-    u64 nchunks = 0;
 };
 
 extern "C" int ua_pbatch_create(ua_ctx *c, const uint64_t *bases, const uint32_t *num_uids,
@@ -3025,23 +2976,24 @@ extern "C" int ua_pbatch_create(ua_ctx *c, const uint64_t *bases, const uint32_t
     HIP_TRY(hipSetDevice(c->device));
     if (n_packs <= 0) return UA_ERR_INVALID;
     ua_pbatch *b = new ua_pbatch();
-    b->n_packs = n_packs;
-    b->nb = pack_block_base[n_packs];
-    b->bases = bases;
-    b->nums = num_uids;
-    b->doffs = delta_offs;
-    b->deltas = deltas;
+    UaFan &f = b->fan;
+    f.n_packs = n_packs;
+    f.nb = pack_block_base[n_packs];
+    f.bases = bases;
+    f.nums = num_uids;
+    f.doffs = delta_offs;
+    f.deltas = deltas;
     for (int p = 0; p < n_packs; p++) b->sum_m += tasks[p].m;
-    b->nchunks = (b->nb + 1 + UA_SCAN_CHUNK - 1) / UA_SCAN_CHUNK;
+    f.nchunks = scan_chunks(f.nb + 1);
 
     size_t o_pbb = 0;
     size_t o_tasks = align16(o_pbb + ((size_t)n_packs + 1) * sizeof(u64));
     size_t o_cnt = align16(o_tasks + (size_t)n_packs * sizeof(ua_ptask));
-    size_t o_offs = align16(o_cnt + (b->nb + 1) * sizeof(u32));
-    size_t o_part = align16(o_offs + (b->nb + 1) * sizeof(u64));
-    size_t o_pout = align16(o_part + (b->nchunks + 1) * sizeof(u64));
+    size_t o_offs = align16(o_cnt + (f.nb + 1) * sizeof(u32));
+    size_t o_part = align16(o_offs + (f.nb + 1) * sizeof(u64));
+    size_t o_pout = align16(o_part + (f.nchunks + 1) * sizeof(u64));
     size_t o_stage = align16(o_pout + (size_t)n_packs * sizeof(u64));
-    size_t total = align16(o_stage + (b->nb ? b->nb : 1) * UA_MAX_BLOCK_UIDS * sizeof(u64));
+    size_t total = align16(o_stage + (f.nb ? f.nb : 1) * UA_MAX_BLOCK_UIDS * sizeof(u64));
     hipError_t e = hipMalloc(&b->mem, total);
     if (e != hipSuccess) {
         g_last_hip = e;
@@ -3049,26 +3001,26 @@ extern "C" int ua_pbatch_create(ua_ctx *c, const uint64_t *bases, const uint32_t
         return UA_ERR_NOMEM;
     }
     u8 *base8 = (u8 *)b->mem;
-    b->d_pbb = (u64 *)(base8 + o_pbb);
-    b->d_tasks = (ua_ptask *)(base8 + o_tasks);
-    b->d_cnt = (u32 *)(base8 + o_cnt);
-    b->d_offs = (u64 *)(base8 + o_offs);
-    b->d_part = (u64 *)(base8 + o_part);
-    b->d_pout = (u64 *)(base8 + o_pout);
-    b->d_stage = (u64 *)(base8 + o_stage);
+    f.pbb = (const u64 *)(base8 + o_pbb);
+    f.tasks = (const ua_ptask *)(base8 + o_tasks);
+    f.cnt = (u32 *)(base8 + o_cnt);
+    f.offs = (u64 *)(base8 + o_offs);
+    f.part = (u64 *)(base8 + o_part);
+    f.pout = (u64 *)(base8 + o_pout);
+    f.stage = (u64 *)(base8 + o_stage);
 
     std::vector<u8> hostbuf(o_cnt);
     memcpy(hostbuf.data(), pack_block_base, ((size_t)n_packs + 1) * sizeof(u64));
     memcpy(hostbuf.data() + o_tasks, tasks, (size_t)n_packs * sizeof(ua_ptask));
     HIP_TRY(hipMemcpyAsync(b->mem, hostbuf.data(), hostbuf.size(),
                            hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(b->d_cnt + b->nb, 0, sizeof(u32), c->stream));
+    HIP_TRY(hipMemsetAsync(f.cnt + f.nb, 0, sizeof(u32), c->stream));
     u64 db = 0;
-    HIP_TRY(hipMemcpyAsync(&db, delta_offs + b->nb, sizeof(u64),
+    HIP_TRY(hipMemcpyAsync(&db, delta_offs + f.nb, sizeof(u64),
                            hipMemcpyDeviceToHost, c->stream));
-    int vrc = (b->nb > 0) ? pack_validate_begin(c, num_uids, delta_offs, b->nb) : UA_OK;
+    int vrc = (f.nb > 0) ? pack_validate_begin(c, num_uids, delta_offs, f.nb) : UA_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (vrc == UA_OK && b->nb > 0) vrc = pack_validate_end(c);
+    if (vrc == UA_OK && f.nb > 0) vrc = pack_validate_end(c);
     if (vrc != UA_OK) {
         ua_pbatch_destroy(c, b);
         return vrc;
@@ -3088,40 +3040,10 @@ extern "C" void ua_pbatch_destroy(ua_ctx *c, ua_pbatch *b) {
 extern "C" int ua_pbatch_run(ua_ctx *c, ua_pbatch *b, uint64_t *out_lens) {
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    u64 nb = b->nb;
-    if (nb > 0) {
-        u64 nwg = (nb + UA_PKW - 1) / UA_PKW;
-        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        hipLaunchKernelGGL(k_packed<0>, dim3((u32)nwg), dim3(UA_BLOCK), 0, c->stream,
-                           b->bases, b->nums, b->doffs, b->deltas, nb, (u64)0,
-                           (const u64 *)nullptr, (u64)0, b->d_stage, b->d_cnt,
-                           b->d_pbb, b->n_packs, b->d_tasks);
-        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-        hipLaunchKernelGGL(k_scan1, dim3((u32)b->nchunks), dim3(UA_BLOCK), 0, c->stream,
-                           b->d_cnt, nb + 1, b->d_offs, b->d_part);
-        hipLaunchKernelGGL(k_scan2, dim3(1), dim3(UA_BLOCK), 0, c->stream, b->d_part,
-                           b->nchunks);
-        hipLaunchKernelGGL(k_compact_pack, dim3((u32)((nb + 15) / 16)), dim3(UA_BLOCK),
-                           0, c->stream, b->d_tasks, b->d_pbb, b->n_packs, b->d_cnt,
-                           b->d_offs, b->d_part, b->d_stage, nb);
-    }
-    u64 poutblk = ((u64)b->n_packs + UA_BLOCK - 1) / UA_BLOCK;
-    hipLaunchKernelGGL(k_pair_out, dim3((u32)poutblk), dim3(UA_BLOCK), 0, c->stream,
-                       b->d_offs, b->d_part, b->d_pbb, b->n_packs, b->d_pout);
-    HIP_TRY(hipMemcpyAsync(out_lens, b->d_pout, (size_t)b->n_packs * sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
-    if (nb > 0) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        c->kernel_ms += ms;
-        c->n_launches += 1;
-    }
-    u64 out_elems = 0;
-    for (int p = 0; p < b->n_packs; p++) out_elems += out_lens[p];
-    c->bytes_algo += b->deltas_bytes + nb * 20 + 8 * (b->sum_m + out_elems);
-    return UA_OK;
+    int rc;
+    if ((rc = enqueue_packed_fanout(c, b->fan))) return rc;
+    if ((rc = packed_fanout_lens(c, b->fan, out_lens))) return rc;
+    return packed_fanout_stats(c, b->fan, out_lens, b->deltas_bytes, b->sum_m);
 }
 
 /* ---- GPU codec.Encode pipeline (codec.go:393 semantics, engine layout) ---- */
@@ -3154,13 +3076,13 @@ extern "C" int ua_encode_dev(ua_ctx *c, const uint64_t *uids, uint64_t n,
     HIP_TRY(hipMemsetAsync(d_flags + n, 0, sizeof(u32), c->stream));
     hipLaunchKernelGGL(k_enc_msb_flags, dim3((u32)nblk), dim3(UA_BLOCK), 0, c->stream,
                        uids, n, d_flags);
-    if ((rc = run_scan(c, d_flags, n + 1, d_offs))) return rc;
+    if ((rc = ws_scan(c, d_flags, n + 1, d_offs))) return rc;
     u64 *d_part = (u64 *)c->ws[WS_PARTIAL];
     hipLaunchKernelGGL(k_enc_mark_start, dim3((u32)nblk1), dim3(UA_BLOCK), 0, c->stream,
                        d_flags, d_offs, d_part, n, d_run);
     hipLaunchKernelGGL(k_enc_block_flags, dim3((u32)nblk), dim3(UA_BLOCK), 0, c->stream,
                        d_flags, d_offs, d_part, d_run, n, block_size);
-    if ((rc = run_scan(c, d_flags, n + 1, d_offs))) return rc;
+    if ((rc = ws_scan(c, d_flags, n + 1, d_offs))) return rc;
     d_part = (u64 *)c->ws[WS_PARTIAL];
     hipLaunchKernelGGL(k_enc_mark_start, dim3((u32)nblk1), dim3(UA_BLOCK), 0, c->stream,
                        d_flags, d_offs, d_part, n, d_bstart);
@@ -3179,7 +3101,7 @@ extern "C" int ua_encode_dev(ua_ctx *c, const uint64_t *uids, uint64_t n,
                        d_flags, d_stage);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     HIP_TRY(hipMemsetAsync(d_flags + nb, 0, sizeof(u32), c->stream));
-    if ((rc = run_scan(c, d_flags, nb + 1, d_offs))) return rc;
+    if ((rc = ws_scan(c, d_flags, nb + 1, d_offs))) return rc;
     d_part = (u64 *)c->ws[WS_PARTIAL];
     hipLaunchKernelGGL(k_enc_finalize, dim3((u32)((nb + 1 + 3) / 4)), dim3(UA_BLOCK), 0,
                        c->stream, d_stage, d_flags, d_offs, d_part, nb, deltas, delta_offs);
@@ -3193,10 +3115,7 @@ extern "C" int ua_encode_dev(ua_ctx *c, const uint64_t *uids, uint64_t n,
     *n_blocks_out = nb;
     *deltas_bytes_out = db_off + db_part;
 
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->kernel_ms += ms;
-    c->n_launches += 1;
+    if ((rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
     c->bytes_algo += 8 * n + (db_off + db_part) + nb * 20;
     return UA_OK;
 }
