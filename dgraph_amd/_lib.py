@@ -59,6 +59,19 @@ class UaDSeg(C.Structure):
     ]
 
 
+class UaDRows(C.Structure):
+    _fields_ = [
+        ("vals", C.c_void_p),
+        ("row_offs", C.c_void_p),
+        ("n_rows", _u64),
+        ("total", _u64),
+        ("shared", C.c_void_p),
+        ("m", _u64),
+        ("out_vals", C.c_void_p),
+        ("out_row_offs", C.c_void_p),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -124,6 +137,9 @@ def lib():
         L.ua_apply_filter_batch_dev.argtypes = [C.c_void_p, C.POINTER(UaDFilter),
                                                 C.c_int, _u64p]
         L.ua_apply_filter.argtypes = [C.c_void_p, _u64p, _u64, _u8p, _u64p]
+        L.ua_rows_filter_dev.argtypes = [C.c_void_p, C.POINTER(UaDRows), C.c_int, _u64p]
+        L.ua_rows_filter.argtypes = [C.c_void_p, _u64p, _u64p, _u64, _u64p, _u64, C.c_int,
+                                     _u64p, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

@@ -225,6 +225,44 @@ class Engine:
             C.c_void_p(out.data_ptr())))
         return out
 
+    def filter_rows(self, vals, row_offs, shared, mode=0, out_vals=None,
+                    out_row_offs=None):
+        """Row-wise UID-matrix filter against one shared sorted list
+        (ua_rows_filter_dev): updateUidMatrix, query/query.go:1425-1437, and
+        the worker/task.go:1352,1617,1692,1778 per-row IntersectWith loops as
+        ONE grid over the flat element array.  vals (rows concatenated),
+        row_offs (n_rows+1) and shared are CUDA int64 tensors holding u64
+        bits; rows need not be sorted.  mode is ROWS_INTERSECT or
+        ROWS_DIFFERENCE.  Returns (out_vals[:kept], out_row_offs); the
+        outputs must not alias the inputs."""
+        import torch
+        from dgraph_amd._lib import UaDRows
+        total = vals.numel()
+        n_rows = row_offs.numel() - 1
+        if n_rows < 0:
+            raise ValueError("row_offs needs n_rows + 1 entries")
+        if out_vals is None:
+            out_vals = torch.empty(max(total, 1), dtype=torch.int64, device=vals.device)
+        if out_row_offs is None:
+            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=vals.device)
+        if out_vals.numel() < total:
+            raise ValueError(f"out_vals capacity {out_vals.numel()} < required {total}")
+        if out_row_offs.numel() < n_rows + 1:
+            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
+                             f"required {n_rows + 1}")
+        d = UaDRows()
+        d.vals = vals.data_ptr()
+        d.row_offs = row_offs.data_ptr()
+        d.n_rows = n_rows
+        d.total = total
+        d.shared = shared.data_ptr()
+        d.m = shared.numel()
+        d.out_vals = out_vals.data_ptr()
+        d.out_row_offs = out_row_offs.data_ptr()
+        kept = _u64()
+        check(lib().ua_rows_filter_dev(self._ctx, C.byref(d), int(mode), C.byref(kept)))
+        return out_vals[:kept.value], out_row_offs[:n_rows + 1]
+
     # ---- packed (codec) path ----
     def upload_pack(self, bases, num_uids, delta_offs, deltas_blob, block_size):
         """Upload flat pack arrays (from encode_flat) -> DPack on this GPU."""
@@ -399,6 +437,9 @@ OP_INTERSECT = 0
 OP_MERGE = 1
 OP_DIFFERENCE = 2
 
+ROWS_INTERSECT = 0
+ROWS_DIFFERENCE = 1
+
 
 class Batch:
     """Prepared pair batch (ua_batch): run() executes one op over all pairs
@@ -551,6 +592,30 @@ def difference(engine, u, v):
     check(lib().ua_difference(engine._ctx, _hptr(u), u.size, _hptr(v), v.size,
                               _hptr(out), C.byref(n)))
     return out[:n.value]
+
+
+def update_uid_matrix(engine, rows, dest_uids, ordered=False, mode=ROWS_INTERSECT):
+    """updateUidMatrix (query/query.go:1425-1437) and the worker/task.go:1352,
+    1617,1692,1778 loops as ONE call (ua_rows_filter): every row filtered by
+    membership in the sorted dest_uids.  rows: list of host uint64 arrays;
+    returns a list of host arrays.  `ordered` only names the reference branch
+    the caller is on (IntersectWith per row, or ApplyFilter+IndexOf when the
+    rows are not uid-sorted): the computation is the same."""
+    arrs = [_np_u64(r) for r in rows]
+    n_rows = len(arrs)
+    row_offs = np.zeros(n_rows + 1, dtype=np.uint64)
+    if n_rows:
+        row_offs[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+    vals = np.ascontiguousarray(np.concatenate(arrs), dtype=np.uint64) if n_rows else \
+        np.empty(0, dtype=np.uint64)
+    shared = _np_u64(dest_uids)
+    out_vals = np.empty(max(vals.size, 1), dtype=np.uint64)
+    out_offs = np.empty(n_rows + 1, dtype=np.uint64)
+    kept = _u64()
+    check(lib().ua_rows_filter(engine._ctx, _hptr(vals), _hptr(row_offs), n_rows,
+                               _hptr(shared), shared.size, int(mode), _hptr(out_vals),
+                               _hptr(out_offs), C.byref(kept)))
+    return [out_vals[int(out_offs[r]):int(out_offs[r + 1])] for r in range(n_rows)]
 
 
 def _host_lists(lists):

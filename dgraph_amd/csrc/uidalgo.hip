@@ -1489,6 +1489,182 @@ __global__ __launch_bounds__(UA_BLOCK) void k_copy_len(
         out[i] = src[i];
 }
 
+/* ==================== kernels: row-wise UID-matrix filter ====================
+ * N rows x ONE shared sorted list (query/query.go:1425-1437 updateUidMatrix;
+ * worker/task.go:1352,1617,1692,1778): a per-element membership filter over
+ * the FLAT element array of a CSR matrix.  Search-based, not merge path: the
+ * pair path streams the whole shared list once per row (8*(n_i+m) bytes per
+ * row), this reads each element once and probes log2(m) times, the first
+ * ~log2(P) probes in an LDS pivot table and the rest inside one stride-wide
+ * bracket of the shared list (L2 / Infinity-Cache resident).  Rows exist only
+ * as offsets: tiles are cut over the flat array, so row-length skew cannot
+ * unbalance the grid, and k_rows_offs recovers each output offset from the
+ * keep bits.  Nothing communicates across workgroups. */
+
+#define UA_RTILE 2048                       /* flat elements per workgroup */
+#define UA_RSTEPS (UA_RTILE / UA_BLOCK)     /* coalesced 256-wide steps per tile */
+#define UA_RWORDS (UA_RTILE / 64)           /* u64 keep-words per tile */
+#define UA_ROWS_P 1024                      /* pivot table entries (8 KB of LDS) */
+static_assert(UA_RTILE % UA_BLOCK == 0 && UA_RWORDS == 32 && UA_RSTEPS <= 32,
+              "one keep-word per wave-step; k_rows_write scans 32 words in one wave");
+static_assert(UA_ROWS_P % UA_BLOCK == 0 && UA_ROWS_P % 2 == 0, "pivot table geometry");
+
+/* piv[j] = shared[j * stride] for j < npiv; the pad keeps the table's 16-byte
+ * loads defined.  With m <= P the stride is 1 and the table is the list. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rows_pivots(
+    const u64 *__restrict__ shared, u64 stride, u32 npiv, u64 *__restrict__ piv) {
+    u32 j = blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (j < UA_ROWS_P) piv[j] = (j < npiv) ? shared[(u64)j * stride] : ~0ull;
+}
+
+/* Pass 1: membership of every flat element, one ballot word per wave-step,
+ * one keep count per tile.  Both searches look for the LAST entry <= key
+ * (found iff that entry == key) with wave-uniform trip counts: the LDS one
+ * runs over npiv, the global one gsteps times over a bracket of < stride
+ * entries, idling (half == 0) once a lane's bracket is down to one entry.  The
+ * 8 elements of a thread advance together so their probes overlap.  Every
+ * index stays inside [0, npiv) / [0, m) whatever the data, so an unsorted
+ * shared list gives wrong answers but no out-of-bounds access. */
+template <int MODE>
+__global__ __launch_bounds__(UA_BLOCK) void k_rows_probe(
+    const u64 *__restrict__ vals, u64 total, const u64 *__restrict__ shared, u64 m,
+    const u64 *__restrict__ piv_g, u32 npiv, u64 stride, int gsteps,
+    u64 *__restrict__ kw, u32 *__restrict__ tile_cnt) {
+    __shared__ __attribute__((aligned(16))) u64 piv[UA_ROWS_P];
+    __shared__ u32 wsum[UA_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 tile = blockIdx.x;
+
+    const ulonglong2 *src = (const ulonglong2 *)piv_g;
+    ulonglong2 *dst = (ulonglong2 *)piv;
+    for (u32 q = tid; q < (npiv + 1) / 2; q += UA_BLOCK) dst[q] = src[q];
+
+    u64 key[UA_RSTEPS];
+    u32 ok = 0;
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        u64 i = tile * UA_RTILE + (u64)s * UA_BLOCK + tid;
+        bool in = i < total;
+        key[s] = in ? vals[i] : 0;
+        ok |= (u32)in << s;
+    }
+    __syncthreads();
+
+    u32 j[UA_RSTEPS];
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) j[s] = 0;
+    for (u32 n = npiv; n > 1; n -= n >> 1) {
+        u32 half = n >> 1;
+#pragma unroll
+        for (int s = 0; s < UA_RSTEPS; s++)
+            j[s] = (piv[j[s] + half] <= key[s]) ? j[s] + half : j[s];
+    }
+
+    u32 found = 0;
+    u64 base[UA_RSTEPS];
+    u32 len[UA_RSTEPS];
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        u64 pv = npiv ? piv[j[s]] : ~0ull;
+        bool live = npiv && ((ok >> s) & 1);
+        found |= (u32)(live && pv == key[s]) << s;
+        /* pv < key: the key can only sit strictly between this pivot and the next */
+        u64 lo = (u64)j[s] * stride + 1;
+        u64 hi = (u64)(j[s] + 1) * stride;
+        hi = hi < m ? hi : m;
+        bool br = live && pv < key[s] && hi > lo;
+        base[s] = br ? lo : 0;
+        len[s] = br ? (u32)(hi - lo) : 0;
+    }
+    if (stride > 1) { /* m > P: shared[0] exists, so base == 0 is a safe idle probe */
+        for (int k = 0; k < gsteps; k++) {
+#pragma unroll
+            for (int s = 0; s < UA_RSTEPS; s++) {
+                u32 half = len[s] >> 1;
+                u64 v = shared[base[s] + half];
+                base[s] += (v <= key[s]) ? half : 0;
+                len[s] -= half;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < UA_RSTEPS; s++) {
+            u64 v = shared[base[s]];
+            found |= (u32)(len[s] != 0 && v == key[s]) << s;
+        }
+    }
+
+    u32 cnt = 0;
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        bool f = (found >> s) & 1;
+        bool keep = ((ok >> s) & 1) && (MODE == UA_ROWS_DIFFERENCE ? !f : f);
+        u64 w = __ballot(keep); /* lanes past total vote 0 */
+        if (lane == 0) kw[tile * UA_RWORDS + s * (UA_BLOCK / 64) + wv] = w;
+        cnt += (u32)__popcll(w);
+    }
+    if (lane == 0) wsum[wv] = cnt;
+    __syncthreads();
+    if (tid == 0) tile_cnt[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+/* Pass 2: same tile/element mapping; rank = tile offset + kept in earlier
+ * wave-steps + kept lanes below.  No re-search: the keep-words are the answer. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rows_write(
+    const u64 *__restrict__ vals, const u64 *__restrict__ kw,
+    const u64 *__restrict__ offs, const u64 *__restrict__ partials,
+    u64 *__restrict__ out_vals) {
+    __shared__ u64 skw[UA_RWORDS];
+    __shared__ u32 spre[UA_RWORDS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 tile = blockIdx.x;
+    if (wv == 0) { /* wave-uniform: all 64 lanes take the shuffles */
+        u64 w = lane < UA_RWORDS ? kw[tile * UA_RWORDS + lane] : 0;
+        u32 c = (u32)__popcll(w), incl = c;
+#pragma unroll
+        for (int o = 1; o < UA_RWORDS; o <<= 1) {
+            u32 x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        if (lane < UA_RWORDS) {
+            skw[lane] = w;
+            spre[lane] = incl - c;
+        }
+    }
+    __syncthreads();
+    const u64 tbase = d_off(offs, partials, tile);
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        int q = s * (UA_BLOCK / 64) + wv;
+        u64 w = skw[q];
+        if ((w >> lane) & 1) { /* a set bit implies i < total */
+            u64 i = tile * UA_RTILE + (u64)s * UA_BLOCK + tid;
+            out_vals[tbase + spre[q] + (u32)__popcll(w & ((1ull << lane) - 1))] = vals[i];
+        }
+    }
+}
+
+/* One thread per row boundary: the kept count before flat position pos is the
+ * tile's scanned offset plus the popcount of the tile's keep bits below pos.
+ * Needs no per-row descriptor or tile, and any number of boundaries (empty
+ * rows included) may fall into one tile.  row_offs is clamped to total, so a
+ * broken offsets array gives wrong offsets but in-bounds reads. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rows_offs(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total, const u64 *__restrict__ kw,
+    const u64 *__restrict__ offs, const u64 *__restrict__ partials,
+    u64 *__restrict__ out_row_offs) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    u64 pos = row_offs[r];
+    pos = pos < total ? pos : total;
+    u64 t = pos / UA_RTILE; /* == ntiles only with rem == 0: scan has that entry */
+    u32 rem = (u32)(pos % UA_RTILE);
+    u64 acc = d_off(offs, partials, t);
+    const u64 *tw = kw + t * UA_RWORDS;
+    for (u32 k = 0; k < rem / 64; k++) acc += (u64)__popcll(tw[k]);
+    if (rem & 63) acc += (u64)__popcll(tw[rem / 64] & ((1ull << (rem & 63)) - 1));
+    out_row_offs[r] = acc;
+}
+
 /* ==================== host shim ==================== */
 
 static thread_local hipError_t g_last_hip = hipSuccess;
@@ -1505,7 +1681,7 @@ static thread_local hipError_t g_last_hip = hipSuccess;
 enum {
     WS_DESC = 0, WS_TB, WS_TPAIR, WS_TA0, WS_TCNT, WS_TOFF, WS_PARTIAL,
     WS_STAGE, WS_STAGEP, WS_POUT, WS_HU, WS_HV, WS_HOUT, WS_PACK, WS_SCRATCH_A,
-    WS_SCRATCH_B, WS_LOOK, WS_COUNT
+    WS_SCRATCH_B, WS_LOOK, WS_RPIV, WS_RKW, WS_COUNT
 };
 
 struct ua_ctx {
@@ -2524,6 +2700,86 @@ extern "C" int ua_index_of_batch_dev(ua_ctx *c, const uint64_t *u, uint64_t n,
     return UA_OK;
 }
 
+/* ---- row-wise UID-matrix filter against one shared list ----
+ * query/query.go:1425-1437 updateUidMatrix (IntersectWith per row, or
+ * ApplyFilter+IndexOf per row when ordered) and worker/task.go:1352,1617,
+ * 1692,1778 (IntersectWith(UidMatrix[i], filtered, UidMatrix[i]) per row):
+ * all rows in one call, five enqueues, one sync. */
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+extern "C" int ua_rows_filter_dev(ua_ctx *c, const ua_drows *d, int mode,
+                                  uint64_t *out_total) {
+    if (!c || !d || !out_total) return UA_ERR_INVALID;
+    if (mode != UA_ROWS_INTERSECT && mode != UA_ROWS_DIFFERENCE) return UA_ERR_INVALID;
+    const u64 total = d->total, n_rows = d->n_rows, m = d->m;
+    /* tile and row-boundary grids are u32 block counts; stride * P >= m must
+     * keep bracket lengths in u32 */
+    if (total >= ((u64)UA_RTILE << 31) || n_rows >= ((u64)UA_BLOCK << 31) ||
+        m >= ((u64)UA_ROWS_P << 31))
+        return UA_ERR_INVALID;
+    if (n_rows == 0 && total != 0) return UA_ERR_INVALID;
+    /* a packed flat compaction cannot run in place: a tile's writes land in
+     * earlier tiles' input range */
+    if (ranges_overlap(d->vals, total * sizeof(u64), d->out_vals, total * sizeof(u64)) ||
+        ranges_overlap(d->row_offs, (n_rows + 1) * sizeof(u64), d->out_row_offs,
+                       (n_rows + 1) * sizeof(u64)))
+        return UA_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 ntiles = (total + UA_RTILE - 1) / UA_RTILE;
+    const u64 stride = m > UA_ROWS_P ? (m + UA_ROWS_P - 1) / UA_ROWS_P : 1;
+    const u32 npiv = (u32)((m + stride - 1) / stride);
+    int gsteps = 0;
+    while (((u64)1 << gsteps) < stride) gsteps++;
+    int rc;
+    if ((rc = ws_reserve(c, WS_RPIV, UA_ROWS_P * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_RKW, (size_t)(ntiles ? ntiles : 1) * UA_RWORDS * sizeof(u64))))
+        return rc;
+    /* one extra zero count: d_off(ntiles) is the kept total, which a row
+     * boundary at pos == total reads when total is a multiple of the tile */
+    if ((rc = ws_reserve(c, WS_TCNT, (size_t)(ntiles + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (size_t)(ntiles + 1) * sizeof(u64)))) return rc;
+    u64 *d_piv = (u64 *)c->ws[WS_RPIV];
+    u64 *d_kw = (u64 *)c->ws[WS_RKW];
+    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    HIP_TRY(hipMemsetAsync(d_cnt + ntiles, 0, sizeof(u32), c->stream));
+    if (ntiles) {
+        hipLaunchKernelGGL(k_rows_pivots, dim3(UA_ROWS_P / UA_BLOCK), dim3(UA_BLOCK), 0,
+                           c->stream, d->shared, stride, npiv, d_piv);
+        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+        if (mode == UA_ROWS_INTERSECT)
+            hipLaunchKernelGGL(k_rows_probe<UA_ROWS_INTERSECT>, dim3((u32)ntiles),
+                               dim3(UA_BLOCK), 0, c->stream, d->vals, total, d->shared, m,
+                               d_piv, npiv, stride, gsteps, d_kw, d_cnt);
+        else
+            hipLaunchKernelGGL(k_rows_probe<UA_ROWS_DIFFERENCE>, dim3((u32)ntiles),
+                               dim3(UA_BLOCK), 0, c->stream, d->vals, total, d->shared, m,
+                               d_piv, npiv, stride, gsteps, d_kw, d_cnt);
+        HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    }
+    if ((rc = ws_scan(c, d_cnt, ntiles + 1, d_offs))) return rc;
+    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+    if (ntiles)
+        hipLaunchKernelGGL(k_rows_write, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                           d->vals, d_kw, d_offs, d_part, d->out_vals);
+    hipLaunchKernelGGL(k_rows_offs, dim3((u32)(n_rows / UA_BLOCK + 1)), dim3(UA_BLOCK), 0,
+                       c->stream, d->row_offs, n_rows, total, d_kw, d_offs, d_part,
+                       d->out_row_offs);
+    u64 kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, d->out_row_offs + n_rows, sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if (ntiles && (rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
+    c->bytes_algo += 8 * (total + kept);
+    *out_total = kept;
+    return UA_OK;
+}
+
 /* ---- IntersectSorted fold (uidlist.go:297): smallest-first pairwise ---- */
 extern "C" int ua_intersect_k_dev(ua_ctx *c, const uint64_t *const *lists,
                                   const uint64_t *lens, int k, uint64_t *out,
@@ -3430,5 +3686,46 @@ extern "C" int ua_intersect_packed(ua_ctx *c, const ua_pack *pack, uint64_t afte
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     *out_n = len;
+    return UA_OK;
+}
+
+/* host-pointer form of ua_rows_filter_dev: what the cgo shim's
+ * updateUidMatrix loop (query/query.go:1425-1437) and the worker/task.go:1352,
+ * 1617,1692,1778 loops call ONCE instead of once per row.  total is
+ * row_offs[n_rows]; out_vals may be vals and out_row_offs may be row_offs
+ * (the device works on its own buffers). */
+extern "C" int ua_rows_filter(ua_ctx *c, const uint64_t *vals, const uint64_t *row_offs,
+                              uint64_t n_rows, const uint64_t *shared, uint64_t m, int mode,
+                              uint64_t *out_vals, uint64_t *out_row_offs,
+                              uint64_t *out_total) {
+    if (!c || !row_offs || !out_row_offs || !out_total) return UA_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_H* reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 total = row_offs[n_rows];
+    const u64 nro = n_rows + 1;
+    int rc;
+    if ((rc = ws_reserve(c, WS_HU, (total + nro) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_HV, (m ? m : 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (total + nro) * sizeof(u64)))) return rc;
+    u64 *d_vals = (u64 *)c->ws[WS_HU], *d_ro = d_vals + total;
+    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + total;
+    if (total)
+        HIP_TRY(hipMemcpyAsync(d_vals, vals, total * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(d_ro, row_offs, nro * sizeof(u64), hipMemcpyHostToDevice,
+                           c->stream));
+    if (m)
+        HIP_TRY(hipMemcpyAsync(c->ws[WS_HV], shared, m * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    ua_drows d = {d_vals, d_ro, n_rows, total, (const u64 *)c->ws[WS_HV], m, d_ov, d_oro};
+    u64 kept = 0;
+    if ((rc = ua_rows_filter_dev(c, &d, mode, &kept))) return rc;
+    if (kept)
+        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, kept * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out_total = kept;
     return UA_OK;
 }

@@ -210,6 +210,47 @@ typedef struct {
 int ua_apply_filter_batch_dev(ua_ctx *, const ua_dfilter *tasks, int n_tasks,
                               uint64_t *out_lens);
 
+/* Row-wise UID-matrix filter against ONE shared sorted list — the "N rows x
+ * one list" shape of the query path: query/query.go:1425-1437
+ * updateUidMatrix (IntersectWith(row, DestUIDs, row) per row, or, for ordered
+ * queries whose rows are not uid-sorted, ApplyFilter(row, IndexOf(DestUIDs,
+ * uid) >= 0)) and worker/task.go:1352,1617,1692,1778
+ * (IntersectWith(UidMatrix[i], filtered, UidMatrix[i]) per row).
+ *
+ * The matrix is in CSR form: vals[total] are the rows concatenated,
+ * row_offs[n_rows+1] is non-decreasing with row_offs[0] = 0 and
+ * row_offs[n_rows] = total.  Per row r, order preserved:
+ *   UA_ROWS_INTERSECT:  out row r = [x for x in row r if x in shared]
+ *   UA_ROWS_DIFFERENCE: out row r = [x for x in row r if x not in shared]
+ * Output rows are packed: out_vals[0 .. *out_total) is a valid CSR body for
+ * out_row_offs.  This is a per-element membership filter, so rows NEED NOT be
+ * sorted and MAY hold duplicates: it always equals the ApplyFilter+IndexOf
+ * form, and equals algo.IntersectWith / algo.Difference on the parity domain
+ * (duplicate-free sorted rows).  shared must be sorted ascending; if it is
+ * not, the result is unspecified but all accesses stay in bounds.
+ *
+ * out_vals must not overlap vals and out_row_offs must not overlap row_offs:
+ * a packed flat compaction cannot run in place (one workgroup's writes land
+ * in another's input range), so overlapping ranges are rejected with
+ * UA_ERR_INVALID — callers ping-pong two buffers.  A row_offs that violates
+ * the contract gives unspecified offsets but no out-of-bounds access (every
+ * offset is clamped to total; vals is only indexed through [0, total)).
+ * n_rows == 0 (then total must be 0), total == 0 and m == 0 are valid; with
+ * m == 0 intersect yields all-empty rows and difference copies the input.
+ * total < 2^42 (the tile count is 32-bit), else UA_ERR_INVALID.  One stream
+ * sync per call; *out_total is the kept total, == out_row_offs[n_rows]. */
+enum { UA_ROWS_INTERSECT = 0, UA_ROWS_DIFFERENCE = 1 };
+typedef struct {
+    const uint64_t *vals;      /* device, total */
+    const uint64_t *row_offs;  /* device, n_rows+1 */
+    uint64_t n_rows, total;
+    const uint64_t *shared;    /* device, sorted, m */
+    uint64_t m;
+    uint64_t *out_vals;        /* device, capacity total; no overlap with vals */
+    uint64_t *out_row_offs;    /* device, n_rows+1; no overlap with row_offs */
+} ua_drows;
+int ua_rows_filter_dev(ua_ctx *, const ua_drows *, int mode, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -269,6 +310,16 @@ int ua_apply_filter(ua_ctx *, uint64_t *u /* compacted in place */, uint64_t n,
 int ua_intersect_packed(ua_ctx *, const ua_pack *, uint64_t after_uid,
                         const uint64_t *v, uint64_t m, uint64_t *out,
                         uint64_t *out_n);            /* IntersectCompressedWith */
+/* updateUidMatrix (query/query.go:1425-1437) and the worker/task.go:1352,
+ * 1617,1692,1778 per-row IntersectWith loops as ONE call: host form of
+ * ua_rows_filter_dev (same semantics and modes).  vals/row_offs/shared are
+ * host arrays, total = row_offs[n_rows]; the compacted rows go to
+ * out_vals (capacity total) and the new offsets to out_row_offs[n_rows+1].
+ * out_vals may be vals and out_row_offs may be row_offs (the reference's
+ * in-place shape): the device works on its own buffers. */
+int ua_rows_filter(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
+                   uint64_t n_rows, const uint64_t *shared, uint64_t m, int mode,
+                   uint64_t *out_vals, uint64_t *out_row_offs, uint64_t *out_total);
 
 #ifdef __cplusplus
 }
