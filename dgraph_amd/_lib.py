@@ -140,6 +140,8 @@ def lib():
         L.ua_rows_filter_dev.argtypes = [C.c_void_p, C.POINTER(UaDRows), C.c_int, _u64p]
         L.ua_rows_filter.argtypes = [C.c_void_p, _u64p, _u64p, _u64, _u64p, _u64, C.c_int,
                                      _u64p, _u64p, _u64p]
+        L.ua_rows_union_dev.argtypes = [C.c_void_p, C.c_void_p, _u64, C.c_void_p, _u64p]
+        L.ua_rows_union.argtypes = [C.c_void_p, _u64p, _u64, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

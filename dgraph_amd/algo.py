@@ -263,6 +263,25 @@ class Engine:
         check(lib().ua_rows_filter_dev(self._ctx, C.byref(d), int(mode), C.byref(kept)))
         return out_vals[:kept.value], out_row_offs[:n_rows + 1]
 
+    def union_rows(self, vals, out=None):
+        """DestUIDs of a CSR UID matrix (ua_rows_union_dev): the ascending
+        duplicate-free set of vals, the rows concatenated — what
+        algo.MergeSorted(UidMatrix) gives at query/query.go:1874,2290,2505,
+        and also defined when the rows are not uid-sorted.  Row offsets are
+        not needed.  vals: CUDA int64 tensor holding u64 bits; out, if given,
+        needs capacity vals.numel() and may be vals itself (no other
+        overlap).  Returns out[:n]."""
+        import torch
+        total = vals.numel()
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.int64, device=vals.device)
+        if out.numel() < total:
+            raise ValueError(f"out capacity {out.numel()} < required {total}")
+        n = _u64()
+        check(lib().ua_rows_union_dev(self._ctx, C.c_void_p(vals.data_ptr()), total,
+                                      C.c_void_p(out.data_ptr()), C.byref(n)))
+        return out[:n.value]
+
     # ---- packed (codec) path ----
     def upload_pack(self, bases, num_uids, delta_offs, deltas_blob, block_size):
         """Upload flat pack arrays (from encode_flat) -> DPack on this GPU."""
@@ -616,6 +635,34 @@ def update_uid_matrix(engine, rows, dest_uids, ordered=False, mode=ROWS_INTERSEC
                                _hptr(shared), shared.size, int(mode), _hptr(out_vals),
                                _hptr(out_offs), C.byref(kept)))
     return [out_vals[int(out_offs[r]):int(out_offs[r + 1])] for r in range(n_rows)]
+
+
+def dest_uids(engine, rows):
+    """DestUIDs = MergeSorted(UidMatrix) (query/query.go:1874,2290,2505,
+    recurse.go:134, worker/task.go:1629,1706) as ONE call (ua_rows_union)
+    over the rows' concatenation: the ascending duplicate-free set of every
+    uid in the matrix.  rows: list of host uint64 arrays, sorted or not, with
+    or without duplicates; returns a host array.  The counterpart of
+    update_uid_matrix."""
+    arrs = [_np_u64(r).ravel() for r in rows]
+    vals = np.ascontiguousarray(np.concatenate(arrs), dtype=np.uint64) if arrs else \
+        np.empty(0, dtype=np.uint64)
+    out = np.empty(max(vals.size, 1), dtype=np.uint64)
+    n = _u64()
+    check(lib().ua_rows_union(engine._ctx, _hptr(vals), vals.size, _hptr(out), C.byref(n)))
+    return out[:n.value]
+
+
+def update_dest_uids(engine, rows, dest):
+    """updateDestUids (query/query.go:2594-2609), the ordered-query fallback
+    for rows that are not uid-sorted ("Can't use merge sort if the UIDs are
+    not sorted", recurse.go:131): keep the uids of dest that occur anywhere in
+    the matrix, in dest's order.  The reference marks IndexOf(dest, uid) per
+    element and compacts; for the sorted duplicate-free dest it always holds
+    that is dest ∩ union(rows): one ua_rows_union plus one pair intersect.
+    rows: list of host uint64 arrays; dest: host uint64 array; returns a host
+    array."""
+    return intersect_with(engine, dest, dest_uids(engine, rows))
 
 
 def _host_lists(lists):

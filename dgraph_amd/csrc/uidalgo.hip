@@ -690,6 +690,113 @@ __global__ __launch_bounds__(UA_BLOCK) void k_sort_chunks(
     for (int i = tid; i < (int)ch.len; i += UA_BLOCK) ch.dst[i] = s[i];
 }
 
+/* k_sort_chunks' bitonic network over s[0..UA_SORT_N) in LDS, ascending, as a
+ * function: every thread of the workgroup calls it (it holds barriers) and s
+ * is complete and visible on return.  A second copy on purpose: calling it
+ * from k_sort_chunks changes that kernel's generated code (the compiler
+ * rotates the outer loop's exit test differently once the loops arrive by
+ * inlining), and the segmented sort's code is pinned. */
+__device__ __forceinline__ void d_bitonic_sort_lds(u64 *s, int tid) {
+    for (int k = 2; k <= UA_SORT_N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < UA_SORT_N; i += UA_BLOCK) {
+                int p = i ^ j;
+                if (p > i) {
+                    bool up = ((i & k) == 0);
+                    u64 x = s[i], y = s[p];
+                    if ((x > y) == up) {
+                        s[i] = y;
+                        s[p] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+/* ==================== kernel: sort-unique leaves of a flat UID matrix ====================
+ * DestUIDs = MergeSorted(rows) (query/query.go:1874,2290,2505, recurse.go:134,
+ * worker/task.go:1629,1706, trigram.go:87, match.go:100) is, as a set, the
+ * sorted distinct values of the flat CSR body vals[0..total) — independent of
+ * the row boundaries.  One workgroup turns UA_SORT_N consecutive flat elements
+ * into one sorted duplicate-free run: runs[leaf*UA_SORT_N ..) of lens[leaf]
+ * values.  The runs are the leaves of the pairwise OP_UNION tree
+ * (union_tree_locked).  Nothing communicates across workgroups.
+ *
+ * The last leaf is padded with UINT64_MAX, which is a legal uid (as is 0): no
+ * value marks "absent".  Only the first len entries of the sorted tile are
+ * real; a real UINT64_MAX tying with the padding is harmless, either copy
+ * lands at an index < len.  A tile that is already non-decreasing (every tile
+ * inside one sorted row) skips the network; the dedup always runs.
+ *
+ * Dedup keeps s[i] iff i == 0 || s[i] != s[i-1].  Elements are owned strided
+ * (i = step*256 + tid, so LDS and global accesses are conflict-free and
+ * coalesced); one ballot per (step, wave) gives the keep-word of 64
+ * consecutive elements, the 32 word counts are scanned by one wave, and an
+ * element's output rank is its word's base plus the popcount below its lane. */
+#define UA_LSTEPS (UA_SORT_N / UA_BLOCK) /* coalesced 256-wide steps per leaf */
+#define UA_LWORDS (UA_SORT_N / 64)       /* keep-words per leaf */
+static_assert(UA_LWORDS == 32 && UA_LSTEPS * (UA_BLOCK / 64) == UA_LWORDS,
+              "one keep-word per (step, wave); one wave scans the 32 word counts");
+
+__global__ __launch_bounds__(UA_BLOCK) void k_union_leaves(
+    const u64 *__restrict__ vals, u64 total, u64 *__restrict__ runs,
+    u64 *__restrict__ lens) {
+    __shared__ u64 s[UA_SORT_N];
+    __shared__ u32 wbase[UA_LWORDS + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 base = (u64)blockIdx.x * UA_SORT_N;
+    if (base >= total) return; /* uniform; the grid is ceil(total / UA_SORT_N) */
+    const int len = (int)((total - base < UA_SORT_N) ? total - base : UA_SORT_N);
+#pragma unroll
+    for (int k = 0; k < UA_LSTEPS; k++) {
+        int i = k * UA_BLOCK + tid;
+        s[i] = (i < len) ? vals[base + i] : UINT64_MAX;
+    }
+    __syncthreads();
+    /* block-wide vote, outside any divergent branch: already non-decreasing?
+     * (the padding is >= every value, so only pairs inside len matter) */
+    int ok = 1;
+#pragma unroll
+    for (int k = 0; k < UA_LSTEPS; k++) {
+        int i = k * UA_BLOCK + tid;
+        if (i + 1 < len && s[i] > s[i + 1]) ok = 0;
+    }
+    if (!__syncthreads_and(ok)) d_bitonic_sort_lds(s, tid); /* uniform branch */
+    u64 v[UA_LSTEPS], kw[UA_LSTEPS];
+#pragma unroll
+    for (int k = 0; k < UA_LSTEPS; k++) {
+        int i = k * UA_BLOCK + tid;
+        v[k] = s[i];
+        bool keep = i < len && (i == 0 || v[k] != s[i - 1]);
+        kw[k] = __ballot(keep);
+        if (lane == 0) wbase[k * (UA_BLOCK / 64) + wv] = (u32)__popcll(kw[k]);
+    }
+    __syncthreads();
+    if (wv == 0) { /* exclusive scan of the 32 word counts; [32] = leaf length */
+        u32 c = lane < UA_LWORDS ? wbase[lane] : 0, incl = c;
+#pragma unroll
+        for (int o = 1; o < UA_LWORDS; o <<= 1) {
+            u32 x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        if (lane < UA_LWORDS) wbase[lane] = incl - c;
+        if (lane == UA_LWORDS - 1) wbase[UA_LWORDS] = incl;
+    }
+    __syncthreads();
+    u64 *dst = runs + base;
+#pragma unroll
+    for (int k = 0; k < UA_LSTEPS; k++) {
+        if ((kw[k] >> lane) & 1) {
+            u32 pos = wbase[k * (UA_BLOCK / 64) + wv] +
+                      (u32)__popcll(kw[k] & (((u64)1 << lane) - 1));
+            dst[pos] = v[k]; /* pos < leaf length <= len */
+        }
+    }
+    if (tid == 0) lens[blockIdx.x] = wbase[UA_LWORDS];
+}
+
 /* ==================== kernels: flat hierarchical scan (u32 -> u64) ==================== */
 
 __global__ __launch_bounds__(UA_BLOCK) void k_scan1(const u32 *__restrict__ cnt, u64 n,
@@ -1681,7 +1788,7 @@ static thread_local hipError_t g_last_hip = hipSuccess;
 enum {
     WS_DESC = 0, WS_TB, WS_TPAIR, WS_TA0, WS_TCNT, WS_TOFF, WS_PARTIAL,
     WS_STAGE, WS_STAGEP, WS_POUT, WS_HU, WS_HV, WS_HOUT, WS_PACK, WS_SCRATCH_A,
-    WS_SCRATCH_B, WS_LOOK, WS_RPIV, WS_RKW, WS_COUNT
+    WS_SCRATCH_B, WS_LOOK, WS_RPIV, WS_RKW, WS_KLEN, WS_COUNT
 };
 
 struct ua_ctx {
@@ -1714,7 +1821,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 11; }
+extern "C" int ua_version(void) { return 12; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -2819,31 +2926,28 @@ extern "C" int ua_intersect_k_dev(ua_ctx *c, const uint64_t *const *lists,
     return UA_OK;
 }
 
-/* ---- MergeSorted k-way (uidlist.go:448): pairwise union tree ---- */
-extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
-                              const uint64_t *lens, int k, uint64_t *out,
-                              uint64_t *out_n) {
-    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: scratch reuse */
-    if (k <= 0) {
-        *out_n = 0;
-        return UA_OK;
-    }
-    if (k == 1) {
-        /* the reference's heap merge dedups even a single list
-         * (TestMergeSorted9: {1,1,1} -> {1}): union with the empty list */
-        ua_dpair pr = {lists[0], lens[0], lists[0], 0, out};
-        return run_batch_locked(c, &pr, 1, out_n, OP_UNION);
-    }
-    /* Device-chained pairwise union tree: positions and tile layouts are
-     * CAPACITY-based (host-known up front), while each round's actual pair
-     * lengths are filled on-device from the previous round's outputs
-     * (k_make_descs) — the whole log2(k)-round tree enqueues with a single
-     * final sync.  Tail tiles past a pair's actual path no-op in k_tiles.
-     * Odd items pair with an empty side (a dedup copy), so every item moves
-     * to the other ping-pong buffer each round. */
-    HIP_TRY(hipSetDevice(c->device));
+/* ---- pairwise union tree over k sorted items (MergeSorted's engine) ----
+ * Device-chained: positions and tile layouts are CAPACITY-based (host-known
+ * up front), while each round's actual pair lengths are filled on-device
+ * from the previous round's outputs (k_make_descs) — the whole log2(k)-round
+ * tree enqueues with a single final sync.  Tail tiles past a pair's actual
+ * path no-op in k_tiles.  Odd items pair with an empty side (a dedup copy),
+ * so every item moves to the other ping-pong buffer each round.
+ *
+ * items/caps are host arrays (device pointers, capacities); d_len0 is a
+ * device array of k u64 that ALREADY holds the items' actual lengths (<= the
+ * capacities) — uploaded by ua_merge_k_dev, written by k_union_leaves for
+ * ua_rows_union_dev — and serves as one half of the rounds' length
+ * ping-pong.  Round r writes WS_SCRATCH_A when r is even and WS_SCRATCH_B
+ * when odd, sum(caps) u64 each, reserved here: items may therefore live in
+ * WS_SCRATCH_B (reserved by the caller at the same size, so this reserve
+ * keeps it), which nothing writes before round 1, when round 0 has consumed
+ * them.  k >= 1; with k == 1 there is no round and the item is copied out.
+ * Books 2 launches per round and the capacity bound of the traffic. */
+static int union_tree_locked(ua_ctx *c, const u64 *const *items, const u64 *item_caps, int k,
+                             u64 *d_len0, u64 *out, u64 *out_n) {
     u64 total = 0;
-    for (int i = 0; i < k; i++) total += lens[i];
+    for (int i = 0; i < k; i++) total += item_caps[i];
     int rc;
     if ((rc = ws_reserve(c, WS_SCRATCH_A, (total ? total : 1) * sizeof(u64)))) return rc;
     if ((rc = ws_reserve(c, WS_SCRATCH_B, (total ? total : 1) * sizeof(u64)))) return rc;
@@ -2858,8 +2962,8 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     std::vector<Round> rounds;
     std::vector<UaDesc> all_descs;
     std::vector<u64> all_tb;
-    std::vector<u64> caps(lens, lens + k);
-    std::vector<const u64 *> ptrs(lists, lists + k);
+    std::vector<u64> caps(item_caps, item_caps + k);
+    std::vector<const u64 *> ptrs(items, items + k);
     u64 max_tiles = 0, cap_work = 0;
     int which = 0;
     while ((int)caps.size() > 1) {
@@ -2898,23 +3002,21 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     }
     int R = (int)rounds.size();
 
-    /* workspace: concat descs+tb+lens ping-pong in WS_DESC; tiles in the
-     * usual slots sized by the largest round */
+    /* workspace: concat descs+tb and the other half of the lens ping-pong
+     * in WS_DESC; tiles in the usual slots sized by the largest round */
     size_t descs_bytes = all_descs.size() * sizeof(UaDesc);
     size_t tb_bytes = all_tb.size() * sizeof(u64);
     size_t lens_bytes = (size_t)k * sizeof(u64);
-    if ((rc = ws_reserve(c, WS_DESC, descs_bytes + tb_bytes + 2 * lens_bytes + 64)))
+    if ((rc = ws_reserve(c, WS_DESC, descs_bytes + tb_bytes + lens_bytes + 64)))
         return rc;
     u8 *wbase = (u8 *)c->ws[WS_DESC];
     UaDesc *d_descs_all = (UaDesc *)wbase;
     u64 *d_tb_all = (u64 *)(wbase + descs_bytes);
-    u64 *d_lens[2] = {(u64 *)(wbase + descs_bytes + tb_bytes),
-                      (u64 *)(wbase + descs_bytes + tb_bytes + lens_bytes)};
-    {
-        std::vector<u8> hostbuf(descs_bytes + tb_bytes + lens_bytes);
+    u64 *d_lens[2] = {d_len0, (u64 *)(wbase + descs_bytes + tb_bytes)};
+    if (descs_bytes + tb_bytes) {
+        std::vector<u8> hostbuf(descs_bytes + tb_bytes);
         memcpy(hostbuf.data(), all_descs.data(), descs_bytes);
         memcpy(hostbuf.data() + descs_bytes, all_tb.data(), tb_bytes);
-        memcpy(hostbuf.data() + descs_bytes + tb_bytes, lens, lens_bytes);
         HIP_TRY(hipMemcpyAsync(wbase, hostbuf.data(), hostbuf.size(),
                                hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream)); /* hostbuf is scoped */
@@ -2971,6 +3073,79 @@ extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
     if ((rc = stats_add(c, c->ev[0], c->ev[1], 2 * R))) return rc;
     c->bytes_algo += 8 * 3 * cap_work; /* capacity upper bound (union count+write) */
     *out_n = final_len;
+    return UA_OK;
+}
+
+/* ---- MergeSorted k-way (uidlist.go:448): pairwise union tree ---- */
+extern "C" int ua_merge_k_dev(ua_ctx *c, const uint64_t *const *lists,
+                              const uint64_t *lens, int k, uint64_t *out,
+                              uint64_t *out_n) {
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: scratch reuse */
+    if (k <= 0) {
+        *out_n = 0;
+        return UA_OK;
+    }
+    if (k == 1) {
+        /* the reference's heap merge dedups even a single list
+         * (TestMergeSorted9: {1,1,1} -> {1}): union with the empty list */
+        ua_dpair pr = {lists[0], lens[0], lists[0], 0, out};
+        return run_batch_locked(c, &pr, 1, out_n, OP_UNION);
+    }
+    /* one leaf per list, capacity == length; the tree's sync after its own
+     * upload covers this one, so the caller's lens need not outlive the call */
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ws_reserve(c, WS_KLEN, (size_t)k * sizeof(u64)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->ws[WS_KLEN], lens, (size_t)k * sizeof(u64),
+                           hipMemcpyHostToDevice, c->stream));
+    return union_tree_locked(c, lists, lens, k, (u64 *)c->ws[WS_KLEN], out, out_n);
+}
+
+/* ---- DestUIDs of a CSR UID matrix: flat sort-unique (k_union_leaves) + the
+ * union tree over ceil(total / 2048) fixed-size leaves ----
+ * The leaves are written to WS_SCRATCH_B, the ping-pong half round 0 does not
+ * write, and their lengths to WS_KLEN, both on the device: no per-row
+ * descriptors, no offsets on the host.  vals is consumed by the leaf kernel
+ * before anything writes out (k_copy_len, last), so out may be vals.
+ * The argument checks come before c is touched. */
+extern "C" int ua_rows_union_dev(ua_ctx *c, const uint64_t *vals, uint64_t total,
+                                 uint64_t *out, uint64_t *out_n) {
+    if (!out_n) return UA_ERR_INVALID;
+    if (total && (!vals || !out)) return UA_ERR_INVALID;
+    /* the tree counts items and pairs in int */
+    if (total > (u64)INT32_MAX * UA_SORT_N) return UA_ERR_INVALID;
+    if (out != vals && ranges_overlap(vals, total * sizeof(u64), out, total * sizeof(u64)))
+        return UA_ERR_INVALID;
+    if (!c) return UA_ERR_INVALID;
+    if (total == 0) {
+        *out_n = 0;
+        return UA_OK;
+    }
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: scratch reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const int nleaf = (int)((total + UA_SORT_N - 1) / UA_SORT_N);
+    int rc;
+    /* the sizes union_tree_locked reserves: its own reserve must not move them */
+    if ((rc = ws_reserve(c, WS_SCRATCH_A, total * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_SCRATCH_B, total * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_KLEN, (size_t)nleaf * sizeof(u64)))) return rc;
+    u64 *runs = (u64 *)c->ws[WS_SCRATCH_B];
+    u64 *d_len = (u64 *)c->ws[WS_KLEN];
+    std::vector<const u64 *> items(nleaf);
+    std::vector<u64> caps(nleaf);
+    for (int i = 0; i < nleaf; i++) {
+        items[i] = runs + (u64)i * UA_SORT_N;
+        caps[i] = std::min<u64>(UA_SORT_N, total - (u64)i * UA_SORT_N);
+    }
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    hipLaunchKernelGGL(k_union_leaves, dim3((u32)nleaf), dim3(UA_BLOCK), 0, c->stream, vals,
+                       total, runs, d_len);
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if ((rc = union_tree_locked(c, items.data(), caps.data(), nleaf, d_len, out, out_n)))
+        return rc;
+    /* the tree has synced the stream: both leaf events are complete */
+    if ((rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    c->bytes_algo += 16 * total; /* leaf pass: read vals, write runs (upper bound) */
     return UA_OK;
 }
 
@@ -3727,5 +3902,35 @@ extern "C" int ua_rows_filter(ua_ctx *c, const uint64_t *vals, const uint64_t *r
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out_total = kept;
+    return UA_OK;
+}
+
+/* host-pointer form of ua_rows_union_dev: DestUIDs = MergeSorted(UidMatrix)
+ * (query/query.go:1874,2290,2505) over the rows' concatenation, sorted or
+ * not.  The device works in place on its own copy, so out may overlap vals
+ * in any way. */
+extern "C" int ua_rows_union(ua_ctx *c, const uint64_t *vals, uint64_t total, uint64_t *out,
+                             uint64_t *out_n) {
+    if (!out_n) return UA_ERR_INVALID;
+    if (total && (!vals || !out)) return UA_ERR_INVALID;
+    if (!c) return UA_ERR_INVALID;
+    if (total == 0) {
+        *out_n = 0;
+        return UA_OK;
+    }
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_H* reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ws_reserve(c, WS_HU, total * sizeof(u64)))) return rc;
+    u64 *d_vals = (u64 *)c->ws[WS_HU];
+    HIP_TRY(hipMemcpyAsync(d_vals, vals, total * sizeof(u64), hipMemcpyHostToDevice,
+                           c->stream));
+    u64 len = 0;
+    if ((rc = ua_rows_union_dev(c, d_vals, total, d_vals, &len))) return rc;
+    if (len)
+        HIP_TRY(hipMemcpyAsync(out, d_vals, len * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out_n = len;
     return UA_OK;
 }

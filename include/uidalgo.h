@@ -251,6 +251,33 @@ typedef struct {
 } ua_drows;
 int ua_rows_filter_dev(ua_ctx *, const ua_drows *, int mode, uint64_t *out_total);
 
+/* DestUIDs of a CSR UID matrix — algo.MergeSorted(UidMatrix) as the query
+ * path calls it: query/query.go:1874, 2290, 2505, query/recurse.go:134,
+ * worker/task.go:1629, 1706, worker/trigram.go:87, worker/match.go:100 — and,
+ * for ordered queries whose rows are not uid-sorted, the set the reference's
+ * updateDestUids fallback (query/query.go:2594-2609) filters DestUIDs by.
+ *
+ * out[0 .. *out_n) is the ascending duplicate-free set of the values in
+ * vals[0 .. total), the matrix's rows concatenated.  As a set DestUIDs does
+ * not depend on the row boundaries, so row_offs is NOT an argument: only
+ * total = row_offs[n_rows] matters.  The call is defined for ANY order and
+ * ANY duplicates in vals; whenever every row is sorted it equals
+ * algo.MergeSorted(rows), rows with duplicates included (MergeSorted
+ * collapses those too, uidlist.go:417).  0 and UINT64_MAX are ordinary
+ * values; all comparisons are unsigned 64-bit.
+ *
+ * The flat array is cut into ceil(total / 2048) tiles, each sorted and
+ * deduplicated by one workgroup, and the tiles are united by the pairwise
+ * tree of ua_merge_k_dev: the work does not depend on the row lengths.
+ * out may be vals EXACTLY (vals is consumed before out is written); any
+ * other overlap of the two ranges is rejected with UA_ERR_INVALID.
+ * total == 0 is valid (*out_n = 0, no launch).  A null ctx, a null out_n, or
+ * a null vals/out with total > 0 give UA_ERR_INVALID.  The tile count must
+ * fit the tree's int item counts: total <= (2^31 - 1) * 2048, else
+ * UA_ERR_INVALID.  Engine scratch: 2 * total u64. */
+int ua_rows_union_dev(ua_ctx *, const uint64_t *vals /* device */, uint64_t total,
+                      uint64_t *out /* device, capacity total */, uint64_t *out_n);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -320,6 +347,13 @@ int ua_intersect_packed(ua_ctx *, const ua_pack *, uint64_t after_uid,
 int ua_rows_filter(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
                    uint64_t n_rows, const uint64_t *shared, uint64_t m, int mode,
                    uint64_t *out_vals, uint64_t *out_row_offs, uint64_t *out_total);
+/* DestUIDs = MergeSorted(UidMatrix) (query/query.go:1874, 2290, 2505 and the
+ * other callers listed at ua_rows_union_dev) over the rows' concatenation:
+ * host form of ua_rows_union_dev, same semantics and checks.  vals and out
+ * are host arrays, total = row_offs[n_rows]; the device works on its own
+ * buffer, so out may overlap vals in any way. */
+int ua_rows_union(ua_ctx *, const uint64_t *vals /* host */, uint64_t total,
+                  uint64_t *out /* host, capacity total */, uint64_t *out_n);
 
 #ifdef __cplusplus
 }
