@@ -433,14 +433,21 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         inputs immutable, so splits are run-invariant like the tile
         partition); null = compute */,
     u32 *__restrict__ isplit_out /* store packed splits on the first run */) {
-    __shared__ __align__(16) u64 smem[UA_SMEMN];
+    /* tile LDS + two boundary slots (union's a_before / b_before) */
+    __shared__ __align__(16) u64 smem[UA_SMEMN + 2];
     __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
-    __shared__ u64 s_abefore;
-    __shared__ u64 s_bbefore;
+    constexpr int SLOT_AB = UA_SMEMN, SLOT_BB = UA_SMEMN + 1;
 
     u64 t = blockIdx.x;
     int tid = threadIdx.x;
+    /* all four tile words are requested together (one scalar round trip);
+     * the neighbour index is clamped, not branched on, so nothing past the
+     * arrays is read and no load waits on another's result */
+    u64 tn = (t + 1 < total_tiles) ? t + 1 : t;
     u32 p = tile_pair[t];
+    u32 pn = tile_pair[tn];
+    u32 a0 = tile_a0[t];
+    u32 a0n = tile_a0[tn];
     UaDesc d = descs[p];
     u64 lt = t - d.tile_base;
     u64 path = d.n + d.m;
@@ -448,18 +455,15 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     if (d0 > path) d0 = path; /* capacity-tiled batches can overshoot the path */
     u64 d1 = d0 + UA_TILE;
     if (d1 > path) d1 = path;
-    u32 a0 = tile_a0[t];
-    u32 a1 = (t + 1 < total_tiles && tile_pair[t + 1] == p) ? tile_a0[t + 1] : (u32)d.n;
+    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
     u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
     int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
-    /* cached splits: issued HERE so the 4B load's latency hides under the
-     * fill drain; consumed only after the barrier */
-    int i0_cached = -1, i0b_cached = -1;
-    if (isplit_in) {
-        u32 w = isplit_in[t * UA_TBLOCK + tid];
-        i0_cached = (int)(w & 0xffffu);
-        i0b_cached = (int)(w >> 16);
-    }
+    /* cached splits: the first vector load of the tile.  The word stays
+     * opaque (split_w is pinned below the barrier) so that no wait stands
+     * between this load and the fill behind it */
+    const bool have_split = (isplit_in != nullptr);
+    u32 split_w = 0;
+    if (have_split) split_w = isplit_in[t * UA_TBLOCK + tid];
 
     /* The fill is global_load_lds (LDS-DMA): +13% over a 16B register-staged
      * fill (4.03 vs 3.58 TB/s on cfg2).  LDS bases are chosen so each side's
@@ -480,12 +484,19 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     bool has_bn = ((u64)b1 < d.m);
 #if UA_ABLATE == 5 /* meta + dispatch floor: no fill, no walk, no scan */
     if (tid == 0) tile_cnt[t] = (u32)((a0 ^ (u32)d.m) & 1u);
-    (void)has_ab; (void)has_bb; (void)has_bn;
+    (void)has_ab; (void)has_bb; (void)has_bn; (void)split_w;
     return;
 #endif
 #if UA_ABLATE != 2
     {
-        /* per-wave LDS-DMA fill: 128 u64 per wave-call (64 lanes x 16 B) */
+        /* Issue everything, wait once.  Per-wave LDS-DMA bodies (128 u64 per
+         * wave-call: 64 lanes x 16 B) for A and B, then each side's
+         * remainder (< 128 elements: one predicated load per thread) and the
+         * boundary elements go to REGISTERS; nothing is waited on until the
+         * single drain below, after which the registers are written to LDS.
+         * A load->wait->ds_write loop here would drain A's LDS-DMA before
+         * B's first load is issued (vmcnt completes in order). */
+        static_assert(UA_TBLOCK >= 128, "one remainder element per thread per side");
         int wv4 = tid >> 6, lane = tid & 63;
         int ahead = ashift; /* elements before the aligned body (0 or 1) */
         if (ahead > alen) ahead = alen;
@@ -495,10 +506,6 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
             __builtin_amdgcn_global_load_lds((const u32 *)g,
                                              (u32 *)&smem[ashift + ahead + e], 16, 0, 0);
         }
-        for (int i = ahead + abody + tid; i < alen; i += UA_TBLOCK)
-            As[i] = d.u[a0 + i];
-        if (tid < ahead) As[tid] = d.u[a0 + tid];
-
         int bhead = bshift;
         if (bhead > blen) bhead = blen;
         int bbody = (blen - bhead) & ~127;
@@ -507,17 +514,39 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
             __builtin_amdgcn_global_load_lds((const u32 *)g,
                                              (u32 *)&smem[boff_base + bhead + e], 16, 0, 0);
         }
-        for (int i = bhead + bbody + tid; i < blen; i += UA_TBLOCK)
-            Bs[i] = d.v[b0 + i];
-        if (tid < bhead) Bs[tid] = d.v[b0 + tid];
-        /* drain the LDS-DMA before the barrier: the glds writes count on
-         * vmcnt, and the compiler's barrier wait cannot be relied on here */
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (tid == 0) {
-        s_abefore = has_ab ? d.u[a0 - 1] : 0;
-        if (OP == OP_UNION) s_bbefore = has_bb ? d.v[b0 - 1] : 0;
-        smem[boff + blen] = has_bn ? d.v[b1] : 0;
+        /* remainders; B's carries the lookahead element d.v[b1] as element
+         * blen when has_bn (else that slot gets 0 and d.v[m] is not read) */
+        int ia = ahead + abody + tid;
+        int ib = bhead + bbody + tid;
+        u64 ra = 0, rb = 0;
+        if (ia < alen) ra = d.u[a0 + ia];
+        if (ib < blen + (has_bn ? 1 : 0)) rb = d.v[b0 + ib];
+        /* boundary elements, one lane each: the two parity heads, and for
+         * union the elements just before the tile (dedup state; no other op
+         * reads them) */
+        const u64 *xsrc = nullptr;
+        int xslot = -1;
+        if (tid == 0) {
+            if (ahead) { xsrc = d.u + a0; xslot = aoff; }
+        } else if (tid == 1) {
+            if (bhead) { xsrc = d.v + b0; xslot = boff; }
+        } else if (OP == OP_UNION && tid == 2) {
+            xslot = SLOT_AB;
+            if (has_ab) xsrc = d.u + a0 - 1;
+        } else if (OP == OP_UNION && tid == 3) {
+            xslot = SLOT_BB;
+            if (has_bb) xsrc = d.v + b0 - 1;
+        }
+        u64 rx = 0;
+        if (xsrc) rx = *xsrc;
+        /* the one drain: the glds writes count on vmcnt and the compiler
+         * does not track them, so its barrier wait cannot be relied on.
+         * The registers pass through it, so whatever wait the compiler adds
+         * for them lands right here and not in front of each LDS write */
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra), "+v"(rb), "+v"(rx)::"memory");
+        if (ia < alen) As[ia] = ra;
+        if (ib <= blen) Bs[ib] = rb;
+        if (xslot >= 0) smem[xslot] = rx;
     }
 #endif
     __syncthreads();
@@ -533,7 +562,7 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     u32 amA = 0, amB = 0;
     int w_i0 = 0, w_i0b = 0;
     int cnt = 0;
-    (void)s_abefore;
+    (void)split_w; (void)have_split;
 #else
     u64 em[UA_WPT];
     u32 flags;
@@ -549,15 +578,20 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     if (smid > tilelen) smid = tilelen;
     if (smid < s0) smid = s0;
     if (smid > s1) smid = s1;
-    int i0 = (i0_cached >= 0) ? i0_cached
-                              : d_merge_path_tile(smem, aoff, alen, boff, blen, s0);
-    int i0b = (i0b_cached >= 0)
-                  ? i0b_cached
-                  : d_merge_path_tile(smem, aoff, alen, boff, blen, smid);
+    int i0, i0b;
+    if (have_split) {
+        /* first use of the cached word, pinned below the barrier */
+        asm volatile("" : "+v"(split_w));
+        i0 = (int)(split_w & 0xffffu);
+        i0b = (int)(split_w >> 16);
+    } else {
+        i0 = d_merge_path_tile(smem, aoff, alen, boff, blen, s0);
+        i0b = d_merge_path_tile(smem, aoff, alen, boff, blen, smid);
+    }
     if (isplit_out)
         isplit_out[t * UA_TBLOCK + tid] = (u32)i0 | ((u32)i0b << 16);
-    u64 a_before = s_abefore;
-    u64 b_before = (OP == OP_UNION) ? s_bbefore : 0;
+    u64 a_before = (OP == OP_UNION) ? smem[SLOT_AB] : 0;
+    u64 b_before = (OP == OP_UNION) ? smem[SLOT_BB] : 0;
     if constexpr (A_ONLY) {
         cnt = tile_walk3x<OP, UA_WPT>(smem, aoff, alen, boff, blen, has_bn,
                                       s0, smid, s1, i0, i0b, flags, amA, amB);
