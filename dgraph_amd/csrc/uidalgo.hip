@@ -74,6 +74,19 @@ static_assert(UA_TILE / UA_TBLOCK >= 1 && UA_TILE / UA_TBLOCK <= 32,
               "emission flags are one u32 bit per path step per thread");
 static_assert(UA_TBLOCK % 64 == 0 && UA_TBLOCK >= 64 && UA_TBLOCK <= 1024,
               "tile kernel is built from whole wavefronts");
+#ifndef UA_FILL_NT
+#define UA_FILL_NT 1 /* 1 = intersect's tile fill (LDS-DMA bodies, remainders,
+                      * boundary elements: every input byte is read once per
+                      * step and little is written) is issued non-temporal;
+                      * 0 = default cache policy.  Union reads its inputs
+                      * twice (COUNT, then WRITE), a merge tree reads what
+                      * the round before wrote, and difference measured
+                      * slower with it on dense tiles: their fills keep the
+                      * default policy, and so do the split words, tile
+                      * words, descs and all stores.  Measured:
+                      * profiles/split_cache.md */
+#endif
+
 static_assert(UA_BLOCK == 256, "wave geometry (4 waves/WG) is hard-coded in "
                                "scan/compact/packed kernels");
 
@@ -101,6 +114,13 @@ __device__ __forceinline__ int d_merge_path_tile(const u64 *smem, int aoff, int 
         else hi = mid;
     }
     return lo;
+}
+
+/* one element of the tile fill, under the fill's cache policy */
+template <bool NT>
+__device__ __forceinline__ u64 d_fill_load(const u64 *p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
 }
 
 /* No scan-3 pass: the flat exclusive scan stays split as (chunk-local offs,
@@ -437,6 +457,9 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     __shared__ __align__(16) u64 smem[UA_SMEMN + 2];
     __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
     constexpr int SLOT_AB = UA_SMEMN, SLOT_BB = UA_SMEMN + 1;
+    /* the fill's cache policy (see UA_FILL_NT); 2 = nt for global_load_lds */
+    constexpr bool FILL_NT = (UA_FILL_NT != 0) && (OP == OP_INTERSECT);
+    constexpr int FILL_AUX = FILL_NT ? 2 : 0;
 
     u64 t = blockIdx.x;
     int tid = threadIdx.x;
@@ -504,7 +527,8 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         for (int e = wv4 * 128; e < abody; e += (UA_TBLOCK / 64) * 128) {
             const u64 *g = d.u + a0 + ahead + e + lane * 2;
             __builtin_amdgcn_global_load_lds((const u32 *)g,
-                                             (u32 *)&smem[ashift + ahead + e], 16, 0, 0);
+                                             (u32 *)&smem[ashift + ahead + e], 16, 0,
+                                             FILL_AUX);
         }
         int bhead = bshift;
         if (bhead > blen) bhead = blen;
@@ -512,15 +536,16 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         for (int e = wv4 * 128; e < bbody; e += (UA_TBLOCK / 64) * 128) {
             const u64 *g = d.v + b0 + bhead + e + lane * 2;
             __builtin_amdgcn_global_load_lds((const u32 *)g,
-                                             (u32 *)&smem[boff_base + bhead + e], 16, 0, 0);
+                                             (u32 *)&smem[boff_base + bhead + e], 16, 0,
+                                             FILL_AUX);
         }
         /* remainders; B's carries the lookahead element d.v[b1] as element
          * blen when has_bn (else that slot gets 0 and d.v[m] is not read) */
         int ia = ahead + abody + tid;
         int ib = bhead + bbody + tid;
         u64 ra = 0, rb = 0;
-        if (ia < alen) ra = d.u[a0 + ia];
-        if (ib < blen + (has_bn ? 1 : 0)) rb = d.v[b0 + ib];
+        if (ia < alen) ra = d_fill_load<FILL_NT>(d.u + a0 + ia);
+        if (ib < blen + (has_bn ? 1 : 0)) rb = d_fill_load<FILL_NT>(d.v + b0 + ib);
         /* boundary elements, one lane each: the two parity heads, and for
          * union the elements just before the tile (dedup state; no other op
          * reads them) */
@@ -538,7 +563,7 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
             if (has_bb) xsrc = d.v + b0 - 1;
         }
         u64 rx = 0;
-        if (xsrc) rx = *xsrc;
+        if (xsrc) rx = d_fill_load<FILL_NT>(xsrc);
         /* the one drain: the glds writes count on vmcnt and the compiler
          * does not track them, so its barrier wait cannot be relied on.
          * The registers pass through it, so whatever wait the compiler adds
@@ -2331,8 +2356,8 @@ struct ua_batch {
     bool stage_p_tried = false;
     /* cached per-thread merge-path splits (valid because the prepared
      * batch's inputs are immutable — same contract as the cached tile
-     * partition): u16 per (tile, thread); written by the first run, read by
-     * every later one */
+     * partition): one u32 per (tile, thread), T * UA_TBLOCK * 4 bytes;
+     * written by the first run of any op, read by every later one */
     u32 *d_isplit = nullptr; /* packed lo16 = i0(s0), hi16 = i0b(smid) */
     bool i0_ready = false;
     /* hipGraph capture of the staged pipeline (per op); out_lens land in the

@@ -142,7 +142,8 @@ int ua_intersect_batch_dev(ua_ctx *, const ua_dpair *pairs, int n_pairs,
 /* Prepared batch (the repeated-query path): descriptor upload and the
  * merge-path tile partition are done ONCE at create; each run is launches
  * only, and the FIRST run additionally caches the per-thread merge-path
- * splits (4 B/tile-thread, device) that every later run loads instead of
+ * splits (4 B per tile-thread = 1 KiB per 2048-element tile, device; one
+ * cache serves all three ops) that every later run loads instead of
  * re-searching.  The pairs' device contents must not change between
  * create and the runs (both caches depend on them; violating this gives
  * unspecified results but stays memory-safe); out capacities must fit the
