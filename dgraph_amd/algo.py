@@ -499,6 +499,15 @@ class Batch:
         check(lib().ua_batch_run_n(self._eng._ctx, self._h, op, n_runs, lens))
         return [int(lens[i]) for i in range(self.n_pairs)]
 
+    def info(self):
+        """ua_batch_info: tile count, tiles that run from the 32-bit copy of
+        the inputs, and that cache's device bytes (0 before the first
+        intersect/difference run, and without the cache)."""
+        t, nt, nb = _u64(), _u64(), _u64()
+        check(lib().ua_batch_info(self._eng._ctx, self._h, C.byref(t), C.byref(nt),
+                                  C.byref(nb)))
+        return {"tiles": t.value, "narrow_tiles": nt.value, "narrow_bytes": nb.value}
+
     def close(self):
         if self._h:
             lib().ua_batch_destroy(self._eng._ctx, self._h)

@@ -103,8 +103,10 @@ __device__ __forceinline__ u64 d_lower_bound(const u64 *__restrict__ a, u64 n, u
 }
 
 /* merge-path split of one tile in LDS: #A consumed after `diag` merge steps,
- * A-priority on ties.  A and B sit at u64 offsets aoff/boff of smem. */
-__device__ __forceinline__ int d_merge_path_tile(const u64 *smem, int aoff, int n,
+ * A-priority on ties.  A and B sit at element offsets aoff/boff of smem
+ * (E = u64, or u32 on a narrow tile: see k_narrow). */
+template <typename E>
+__device__ __forceinline__ int d_merge_path_tile(const E *smem, int aoff, int n,
                                                  int boff, int m, int diag) {
     int lo = diag > m ? diag - m : 0;
     int hi = diag < n ? diag : n;
@@ -380,9 +382,12 @@ __device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int al
  * LDS latency), one mask each.  Viable because the prepared batch caches
  * BOTH splits (i0 at s0, i0b at smid) — round 1 rejected a dual-chain em[]
  * walk precisely because its second diagonal search cost more than the added
- * MLP recovered. */
-template <int OP, int W>
-__device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int alen,
+ * MLP recovered.
+ * E is the LDS element type: u64, or u32 on a narrow tile, whose elements all
+ * share their high 32 bits so that the unsigned 32-bit compares of the low
+ * halves order and match exactly as the 64-bit ones do (see k_narrow). */
+template <int OP, int W, typename E>
+__device__ __forceinline__ int tile_walk3x(const E *smembase, int aoff, int alen,
                                            int boff, int blen, bool has_bn,
                                            int s0, int smid, int s1, int i0a,
                                            int i0b, u32 &flags, u32 &amA, u32 &amB) {
@@ -394,10 +399,10 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
     int ia = i0a, ja = s0 - i0a;
     int ib = i0b, jb = smid - i0b;
     int stepsA = smid - s0, stepsB = s1 - smid;
-    u64 aA = smembase[aoff + (ia < alen ? ia : amax)];
-    u64 bA = smembase[boff + (ja < blen_ext ? ja : bmax)];
-    u64 aB = smembase[aoff + (ib < alen ? ib : amax)];
-    u64 bB = smembase[boff + (jb < blen_ext ? jb : bmax)];
+    E aA = smembase[aoff + (ia < alen ? ia : amax)];
+    E bA = smembase[boff + (ja < blen_ext ? ja : bmax)];
+    E aB = smembase[aoff + (ib < alen ? ib : amax)];
+    E bB = smembase[boff + (jb < blen_ext ? jb : bmax)];
     int cnt = 0;
     flags = 0;
     amA = 0;
@@ -415,7 +420,7 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
             int ni = ia + (takeA ? 1 : 0), nj = ja + (takeA ? 0 : 1);
             int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
                               : (boff + (nj < blen_ext ? nj : bmax));
-            u64 r = smembase[raddr];
+            E r = smembase[raddr];
             aA = takeA ? r : aA;
             bA = takeA ? bA : r;
             ia = ni;
@@ -432,7 +437,7 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
             int ni = ib + (takeA ? 1 : 0), nj = jb + (takeA ? 0 : 1);
             int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
                               : (boff + (nj < blen_ext ? nj : bmax));
-            u64 r = smembase[raddr];
+            E r = smembase[raddr];
             aB = takeA ? r : aB;
             bB = takeA ? bB : r;
             ib = ni;
@@ -440,6 +445,252 @@ __device__ __forceinline__ int tile_walk3x(const u64 *smembase, int aoff, int al
         }
     }
     return cnt;
+}
+
+/* MODE_STAGE: where a thread's emissions go (dst) and how many of them fit
+ * (lim).  Clamped to the staging stride: invalid (duplicate/unsorted) inputs
+ * can emit more than stride entries per tile; results there are unspecified,
+ * OOB writes are not.  Small totals go to the dense primary
+ * region; stage_stride stays the sparse overflow. */
+__device__ __forceinline__ u64 *d_stage_dst(u64 t, int tid, u32 cnt, u32 excl, u32 total,
+                                            u64 *__restrict__ staging, u64 stage_stride,
+                                            const u64 *__restrict__ primary,
+                                            u32 *__restrict__ tile_cnt, u32 &lim) {
+    bool prim = (primary != nullptr) && (total <= UA_STAGE_P);
+    u32 cap_t = prim ? (u32)UA_STAGE_P : (u32)stage_stride;
+    u32 c0 = excl < cap_t ? cap_t - excl : 0;
+    lim = cnt < c0 ? cnt : c0;
+    u64 *dst = prim ? ((u64 *)primary + t * UA_STAGE_P) : (staging + t * stage_stride + excl);
+    if (prim) dst += excl;
+    if (tid == 0) tile_cnt[t] = total < (u32)stage_stride ? total : (u32)stage_stride;
+    return dst;
+}
+
+/* ==================== narrow tiles (prepared batches) ====================
+ * A prepared batch promises that its pairs' device contents do not change
+ * while it lives.  On that promise it keeps, beside the tile partition and
+ * the per-thread splits, a 32-bit tile-major copy of its inputs: one record
+ * per tile, UA_NREC_W u32 at a fixed 16-byte-aligned stride,
+ *
+ *   [0, alen)            low halves of the tile's A range
+ *   [alen, alen + blen)  low halves of its B range
+ *   [.., UA_TILE)        unused (anything; every index is clamped as ever)
+ *   tail, 4 words:       the tile's common high half | low half of B's
+ *                        lookahead d.v[b1] (0 when there is none) | 0 | 0
+ *
+ * A tile is NARROW iff every element of its A range, of its B range and its
+ * lookahead element share one value of x >> 32; k_narrow decides that from
+ * the data, per tile.  Inside such a tile the unsigned compare of two low
+ * halves equals the 64-bit compare, so the walk over the record gives the
+ * wide walk's flags, masks and splits bit for bit, on invalid inputs too.
+ * Every other tile keeps the 64-bit fill and walk.  The record's address
+ * depends on the tile index alone, its source needs no alignment work, and a
+ * step reads 4 B per input element instead of 8. */
+#define UA_NREC_W (UA_TILE + 4) /* u32 per record: UA_TILE low halves + tail */
+#define UA_NARROW_BIT 0x80000000u /* in a batch-private tile-pair word; pair
+                                   * indices are < 2^31 (n_pairs is an int) */
+#define UA_NROUNDS ((UA_TILE * 4) / (UA_TBLOCK * 16)) /* LDS-DMA rounds per record */
+static_assert((UA_TILE * 4) % (UA_TBLOCK * 16) == 0 && UA_NROUNDS >= 1,
+              "a record's data is whole rounds of 16 B per lane");
+static_assert((UA_NREC_W * 4) % 16 == 0, "records stay 16-byte aligned");
+static_assert((UA_TILE + 1) * 4 <= UA_SMEMN * 8, "narrow tile + lookahead fit the tile LDS");
+
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+
+/* Builds the records and votes each tile's eligibility: one workgroup per
+ * tile, list pointers at any 8-byte parity.  tile_pair_n[t] = tile_pair[t],
+ * with UA_NARROW_BIT set on a narrow tile.  Every load of the tile is in
+ * flight at once; thread 0, which holds the tile's first element and the
+ * lookahead, publishes the reference high half through LDS.  A tile whose
+ * partition words do not describe a sane range (possible only on unsorted
+ * input) stays wide and is not copied. */
+__global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
+    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
+    const u32 *__restrict__ tile_a0, u64 total_tiles, u32 *__restrict__ slab,
+    u32 *__restrict__ tile_pair_n) {
+    __shared__ u32 sh_hi;
+    u64 t = blockIdx.x;
+    int tid = threadIdx.x;
+    u64 tn = (t + 1 < total_tiles) ? t + 1 : t;
+    u32 p = tile_pair[t];
+    u32 pn = tile_pair[tn];
+    u32 a0 = tile_a0[t];
+    u32 a0n = tile_a0[tn];
+    UaDesc d = descs[p];
+    /* the tile's ranges, exactly as k_tiles derives them */
+    u64 lt = t - d.tile_base;
+    u64 path = d.n + d.m;
+    u64 d0 = lt * UA_TILE;
+    if (d0 > path) d0 = path;
+    u64 d1 = d0 + UA_TILE;
+    if (d1 > path) d1 = path;
+    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
+    u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
+    int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
+    bool has_bn = ((u64)b1 < d.m);
+    bool sane = alen >= 0 && blen >= 0 && alen + blen >= 1 && alen + blen <= UA_TILE &&
+                (u64)a0 + (u64)alen <= d.n && (u64)b0 + (u64)blen <= d.m;
+    u32 *rec = slab + t * UA_NREC_W;
+    u32 hi = 0, look_lo = 0;
+    int ok = sane ? 1 : 0;
+    if (sane) { /* workgroup-uniform */
+        int tilelen = alen + blen;
+        /* unconditional loads at clamped indices (a thread past the tile's
+         * end re-reads its last element), so that all are issued before any
+         * is waited for; thread 0 adds the lookahead */
+        const u64 *ua = d.u + a0;
+        const u64 *vb = d.v + b0;
+        u64 x[UA_WPT];
+#pragma unroll
+        for (int k = 0; k < UA_WPT; k++) {
+            int e = k * UA_TBLOCK + tid;
+            if (e > tilelen - 1) e = tilelen - 1;
+            const u64 *src = (e < alen) ? ua + e : vb + (e - alen);
+            x[k] = *src;
+        }
+        u64 look = 0;
+        if (tid == 0 && has_bn) look = d.v[b1];
+        if (tid == 0) sh_hi = (u32)(x[0] >> 32); /* element 0 exists: tilelen >= 1 */
+        __syncthreads();
+        hi = sh_hi;
+#pragma unroll
+        for (int k = 0; k < UA_WPT; k++) {
+            /* branch-free: a slot past the tile's end gets the clamped
+             * element's low half, which nothing reads */
+            ok &= ((u32)(x[k] >> 32) == hi);
+            rec[k * UA_TBLOCK + tid] = (u32)x[k];
+        }
+        if (tid == 0 && has_bn) {
+            ok &= ((u32)(look >> 32) == hi);
+            look_lo = (u32)look;
+        }
+    }
+    ok = __syncthreads_and(ok);
+    if (tid == 0) {
+        rec[UA_TILE + 0] = hi;
+        rec[UA_TILE + 1] = look_lo;
+        rec[UA_TILE + 2] = 0;
+        rec[UA_TILE + 3] = 0;
+        tile_pair_n[t] = p | (ok ? UA_NARROW_BIT : 0u);
+    }
+}
+
+/* One narrow tile of k_tiles<OP_INTERSECT | OP_DIFF, MODE_STAGE>: the record
+ * goes to LDS by LDS-DMA as soon as t is known (its address needs no
+ * descriptor), descs[p] arrives behind it, and the walk runs on u32.  Indices,
+ * clamps, masks, the cached split format, the scan and the staging are the
+ * wide path's; emitted A-values get the tile's high half back on the way to
+ * staging. */
+template <int OP>
+__device__ __forceinline__ void tile_narrow(
+    const UaDesc *__restrict__ descs, u32 p, u32 pn, u32 a0, u32 a0n, u64 t, u64 tn,
+    const u32 *__restrict__ slab, u64 *smem, u32 *scan, u64 *__restrict__ staging,
+    u64 stage_stride, u32 *__restrict__ tile_cnt, const u64 *__restrict__ primary,
+    const u32 *__restrict__ isplit_in, u32 *__restrict__ isplit_out) {
+    constexpr bool FILL_NT = (UA_FILL_NT != 0) && (OP == OP_INTERSECT);
+    constexpr int FILL_AUX = FILL_NT ? 2 : 0;
+    int tid = threadIdx.x;
+    /* cached splits: still the first vector load, opaque until the barrier */
+    const bool have_split = (isplit_in != nullptr);
+    u32 split_w = 0;
+    if (have_split) split_w = isplit_in[t * UA_TBLOCK + tid];
+    u32 *s32 = (u32 *)smem;
+    const u32 *rec = slab + t * UA_NREC_W;
+    u32x4 tl = {0, 0, 0, 0}; /* the record's tail: high half, lookahead, 0, 0 */
+#if UA_ABLATE != 2
+    {
+        int wv4 = tid >> 6, lane = tid & 63;
+#pragma unroll
+        for (int r = 0; r < UA_NROUNDS; r++) {
+            int w = (r * (UA_TBLOCK / 64) + wv4) * 256; /* 64 lanes x 16 B = 256 u32 */
+            __builtin_amdgcn_global_load_lds(rec + w + lane * 4, s32 + w, 16, 0, FILL_AUX);
+        }
+        /* the tail, to registers; the opaque zero keeps it a vector load,
+         * in order behind the fill and drained with it */
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        const u32x4 *tp = (const u32x4 *)(rec + UA_TILE) + z;
+        if constexpr (FILL_NT) tl = __builtin_nontemporal_load(tp);
+        else tl = *tp;
+    }
+#endif
+    UaDesc d = descs[p];
+    u64 lt = t - d.tile_base;
+    u64 path = d.n + d.m;
+    u64 d0 = lt * UA_TILE;
+    if (d0 > path) d0 = path;
+    u64 d1 = d0 + UA_TILE;
+    if (d1 > path) d1 = path;
+    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
+    u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
+    int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
+    bool has_bn = ((u64)b1 < d.m);
+    constexpr int aoff = 0;
+    int boff = alen;
+#if UA_ABLATE != 2
+    /* the one drain (see the wide fill); all four tail words pass through
+     * it, so no register of the load is reused, and waited for, earlier */
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(tl)::"memory");
+    if (tid == 0) s32[boff + blen] = tl.y; /* B's lookahead, element blen of B */
+#endif
+    const u32 hiw = tl.x;
+    __syncthreads();
+
+    u32 flags;
+    u32 amA = 0, amB = 0;
+    int w_i0 = 0, w_i0b = 0;
+    int cnt;
+#if UA_ABLATE == 1 /* fill-only */
+    u32 ablate_x = s32[tid] + s32[UA_TILE / 2 + tid];
+    asm volatile("" ::"v"(ablate_x));
+    flags = 0;
+    cnt = 0;
+    (void)split_w; (void)have_split; (void)has_bn; (void)isplit_out; (void)boff;
+#else
+    int tilelen = alen + blen;
+    int s0 = tid * UA_WPT;
+    int s1 = s0 + UA_WPT;
+    if (s0 > tilelen) s0 = tilelen;
+    if (s1 > tilelen) s1 = tilelen;
+    int smid = s0 + UA_WPT / 2;
+    if (smid > tilelen) smid = tilelen;
+    if (smid < s0) smid = s0;
+    if (smid > s1) smid = s1;
+    if (have_split) {
+        asm volatile("" : "+v"(split_w));
+        w_i0 = (int)(split_w & 0xffffu);
+        w_i0b = (int)(split_w >> 16);
+    } else {
+        w_i0 = d_merge_path_tile(s32, aoff, alen, boff, blen, s0);
+        w_i0b = d_merge_path_tile(s32, aoff, alen, boff, blen, smid);
+    }
+    if (isplit_out) isplit_out[t * UA_TBLOCK + tid] = (u32)w_i0 | ((u32)w_i0b << 16);
+    cnt = tile_walk3x<OP, UA_WPT>(s32, aoff, alen, boff, blen, has_bn, s0, smid, s1, w_i0,
+                                  w_i0b, flags, amA, amB);
+#endif
+#if UA_ABLATE == 3 /* fill+walk, skip scan/write-back */
+    asm volatile("" ::"v"(cnt), "v"(flags));
+    cnt = 0;
+    flags = 0;
+#endif
+    u32 excl, total;
+    d_block_scan<UA_TBLOCK>(tid, (u32)cnt, scan, excl, total);
+    u32 lim;
+    u64 *dst = d_stage_dst(t, tid, (u32)cnt, excl, total, staging, stage_stride, primary,
+                           tile_cnt, lim);
+    if (cnt > 0) {
+        constexpr int H = UA_WPT / 2;
+        u64 hi64 = (u64)hiw << 32;
+        u32 f = flags;
+        u32 k = 0;
+        while (f && k < lim) {
+            int s = __builtin_ctz(f);
+            f &= f - 1;
+            int idx = (s < H) ? w_i0 + __popc(amA & ((1u << s) - 1))
+                              : w_i0b + __popc(amB & ((1u << (s - H)) - 1));
+            dst[k++] = hi64 | s32[aoff + idx];
+        }
+    }
 }
 
 template <int OP, int MODE>
@@ -452,7 +703,9 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         PACKED lo16 = i0 at diagonal s0, hi16 = i0b at smid (prepared batch:
         inputs immutable, so splits are run-invariant like the tile
         partition); null = compute */,
-    u32 *__restrict__ isplit_out /* store packed splits on the first run */) {
+    u32 *__restrict__ isplit_out /* store packed splits on the first run */,
+    const u32 *__restrict__ slab /* prepared batch's narrow records (then
+        tile_pair is its private copy with UA_NARROW_BIT), or null */) {
     /* tile LDS + two boundary slots (union's a_before / b_before) */
     __shared__ __align__(16) u64 smem[UA_SMEMN + 2];
     __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
@@ -471,6 +724,18 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     u32 pn = tile_pair[tn];
     u32 a0 = tile_a0[t];
     u32 a0n = tile_a0[tn];
+    if constexpr ((OP == OP_INTERSECT || OP == OP_DIFF) && MODE == MODE_STAGE) {
+        /* eligibility rides in the first scalar round trip: nothing new
+         * stands between it and the fill */
+        const bool narrow = (slab != nullptr) && (p & UA_NARROW_BIT);
+        p &= ~UA_NARROW_BIT;
+        pn &= ~UA_NARROW_BIT;
+        if (narrow) {
+            tile_narrow<OP>(descs, p, pn, a0, a0n, t, tn, slab, smem, scan, staging,
+                            stage_stride, tile_cnt, offs, isplit_in, isplit_out);
+            return;
+        }
+    }
     UaDesc d = descs[p];
     u64 lt = t - d.tile_base;
     u64 path = d.n + d.m;
@@ -661,20 +926,9 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
     u64 *dst;
     u32 lim = (u32)cnt;
     if (MODE == MODE_STAGE) {
-        /* clamp to the staging stride: invalid (duplicate/unsorted) inputs
-         * can emit more than stride entries per tile; results there are
-         * unspecified, OOB writes are not.  Small totals go to
-         * the dense primary region (offs = its base, see enqueue_tiles);
-         * stage_stride stays the sparse overflow. */
-        bool prim = (offs != nullptr) && (total <= UA_STAGE_P);
-        u32 cap_t = prim ? (u32)UA_STAGE_P : (u32)stage_stride;
-        u32 c0 = excl < cap_t ? cap_t - excl : 0;
-        if (lim > c0) lim = c0;
-        dst = prim ? ((u64 *)offs + t * UA_STAGE_P)
-                   : (staging + t * stage_stride + excl);
-        if (prim) dst += excl;
-        if (tid == 0)
-            tile_cnt[t] = total < (u32)stage_stride ? total : (u32)stage_stride;
+        /* offs = the dense primary region's base, see enqueue_tiles */
+        dst = d_stage_dst(t, tid, (u32)cnt, excl, total, staging, stage_stride, offs,
+                          tile_cnt, lim);
     } else { /* MODE_WRITE: (offs, partials) is the split flat scan */
         dst = d.out +
               (d_off(offs, partials, t) - d_off(offs, partials, d.tile_base)) + excl;
@@ -1880,7 +2134,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 12; }
+extern "C" int ua_version(void) { return 13; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -2072,6 +2326,8 @@ struct UaPipe {
     const UaTChunk *cmap = nullptr; /* fused tail's chunk map */
     u64 n_tchunks = 0;       /* 0 = this instance keeps the scanned tail */
     u64 *pout = nullptr;     /* per-pair output lengths */
+    const u32 *slab = nullptr;   /* prepared batch: narrow records (k_narrow) ... */
+    const u32 *tpairn = nullptr; /* ... and tpair with UA_NARROW_BIT, or both null */
 };
 
 /* staging u64 per tile; 0 = the op does not stage (union, merge-all) */
@@ -2093,7 +2349,7 @@ static void enqueue_partition(const UaPipe &p, hipStream_t st) {
 static int enqueue_tiles(const UaPipe &p, int op, int mode, const u32 *isin, u32 *isout,
                          hipStream_t st) {
     void (*k)(const UaDesc *, const u32 *, const u32 *, u64, u64 *, u64, u32 *,
-              const u64 *, const u64 *, const u32 *, u32 *) = nullptr;
+              const u64 *, const u64 *, const u32 *, u32 *, const u32 *) = nullptr;
     if (op == OP_INTERSECT && mode == MODE_STAGE) k = k_tiles<OP_INTERSECT, MODE_STAGE>;
     else if (op == OP_DIFF && mode == MODE_STAGE) k = k_tiles<OP_DIFF, MODE_STAGE>;
     else if (op == OP_UNION && mode == MODE_COUNT) k = k_tiles<OP_UNION, MODE_COUNT>;
@@ -2101,10 +2357,12 @@ static int enqueue_tiles(const UaPipe &p, int op, int mode, const u32 *isin, u32
     else if (op == OP_MERGE_ALL && mode == MODE_DIRECT) k = k_tiles<OP_MERGE_ALL, MODE_DIRECT>;
     else return UA_ERR_INVALID;
     const bool staged = (mode == MODE_STAGE), write = (mode == MODE_WRITE);
-    hipLaunchKernelGGL(k, dim3((u32)p.T), dim3(UA_TBLOCK), 0, st, p.descs, p.tpair, p.ta0,
+    const bool narrow = staged && p.slab && p.tpairn;
+    hipLaunchKernelGGL(k, dim3((u32)p.T), dim3(UA_TBLOCK), 0, st, p.descs,
+                       narrow ? p.tpairn : p.tpair, p.ta0,
                        p.T, staged ? p.stage : nullptr, stage_stride(op), p.tcnt,
                        staged ? p.prim : write ? p.toff : nullptr,
-                       write ? p.part : nullptr, isin, isout);
+                       write ? p.part : nullptr, isin, isout, narrow ? p.slab : nullptr);
     return UA_OK;
 }
 
@@ -2360,6 +2618,15 @@ struct ua_batch {
      * written by the first run of any op, read by every later one */
     u32 *d_isplit = nullptr; /* packed lo16 = i0(s0), hi16 = i0b(smid) */
     bool i0_ready = false;
+    /* third cache, on the same immutability promise: the narrow slab (see
+     * k_narrow), T records of UA_NREC_W u32 + the marked tile-pair words in
+     * ONE allocation, about 4 B per input element.  Built ahead of the first
+     * intersect/difference run; the allocation is tried once (failure or
+     * UA_NARROW=0: the batch runs the 64-bit fill on every tile), a
+     * union-only batch never builds it */
+    void *d_narrow = nullptr;
+    size_t narrow_bytes = 0;
+    bool narrow_tried = false;
     /* hipGraph capture of the staged pipeline (per op); out_lens land in the
      * pinned h_pout so the captured D2H copy has a fixed destination */
     hipGraphExec_t gexec[3][2] = {};
@@ -2440,6 +2707,7 @@ extern "C" void ua_batch_destroy(ua_ctx *c, ua_batch *b) {
     if (b->view[0].prim) (void)hipFree((void *)b->view[0].prim);
     if (b->view[1].stage) (void)hipFree(b->view[1].stage);
     if (b->d_isplit) (void)hipFree(b->d_isplit);
+    if (b->d_narrow) (void)hipFree(b->d_narrow);
     delete b;
 }
 
@@ -2471,6 +2739,61 @@ static void batch_isplit(ua_batch *b, const u32 **isin, u32 **isout) {
         *isout = b->d_isplit;
         b->i0_ready = true; /* ordered: runs are stream-serialized */
     }
+}
+
+/* UA_NARROW=0 keeps every tile of a prepared batch on the 64-bit fill
+ * (same-box A/B); read when the batch first runs a staged op */
+static bool narrow_enabled() {
+    const char *e = getenv("UA_NARROW");
+    return !(e && e[0] == '0');
+}
+
+/* Build the narrow slab ahead of the batch's first staged run: one
+ * allocation attempt per batch, one k_narrow on the engine's stream, outside
+ * the tile kernel's event pair.  Never fatal: without the slab the batch
+ * runs as it always has. */
+static int batch_narrow(ua_ctx *c, ua_batch *b) {
+    if (b->narrow_tried) return UA_OK;
+    b->narrow_tried = true;
+    UaPipe &v0 = b->view[0];
+    if (!narrow_enabled() || v0.T == 0) return UA_OK;
+    size_t o_tpn = align16((size_t)v0.T * UA_NREC_W * sizeof(u32));
+    size_t bytes = align16(o_tpn + (size_t)(v0.T + 1) * sizeof(u32));
+    if (hipMalloc(&b->d_narrow, bytes) != hipSuccess) {
+        b->d_narrow = nullptr;
+        (void)hipGetLastError();
+        return UA_OK;
+    }
+    u8 *base = (u8 *)b->d_narrow;
+    b->narrow_bytes = bytes;
+    hipLaunchKernelGGL(k_narrow, dim3((u32)v0.T), dim3(UA_TBLOCK), 0, c->stream, v0.descs,
+                       v0.tpair, v0.ta0, v0.T, (u32 *)base, (u32 *)(base + o_tpn));
+    v0.slab = (const u32 *)base;
+    v0.tpairn = (const u32 *)(base + o_tpn);
+    if (b->mem1) { /* the overlap set shares the inputs' caches */
+        b->view[1].slab = v0.slab;
+        b->view[1].tpairn = v0.tpairn;
+    }
+    return UA_OK;
+}
+
+extern "C" int ua_batch_info(ua_ctx *c, ua_batch *b, uint64_t *tiles, uint64_t *narrow_tiles,
+                             uint64_t *narrow_bytes) {
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!b) return UA_ERR_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    u64 nn = 0;
+    if (b->view[0].tpairn) { /* count the marked tile-pair words */
+        std::vector<u32> tp((size_t)b->view[0].T);
+        HIP_TRY(hipMemcpyAsync(tp.data(), b->view[0].tpairn, tp.size() * sizeof(u32),
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (u32 w : tp) nn += (w >> 31);
+    }
+    if (tiles) *tiles = b->view[0].T;
+    if (narrow_tiles) *narrow_tiles = nn;
+    if (narrow_bytes) *narrow_bytes = b->d_narrow ? b->narrow_bytes : 0;
+    return UA_OK;
 }
 
 /* the first tile pass of one run (eager; event-timed on the sampled pass) */
@@ -2618,6 +2941,7 @@ static int batch_run_locked(ua_ctx *c, ua_batch *b, int op, int n_runs,
         }
         v0.prim = prim;
     }
+    if (kop != OP_UNION && (rc = batch_narrow(c, b))) return rc;
     if (!b->h_pout) {
         hipError_t e = hipHostMalloc((void **)&b->h_pout, (size_t)n_pairs * sizeof(u64));
         if (e != hipSuccess) {

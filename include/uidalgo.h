@@ -144,9 +144,17 @@ int ua_intersect_batch_dev(ua_ctx *, const ua_dpair *pairs, int n_pairs,
  * only, and the FIRST run additionally caches the per-thread merge-path
  * splits (4 B per tile-thread = 1 KiB per 2048-element tile, device; one
  * cache serves all three ops) that every later run loads instead of
- * re-searching.  The pairs' device contents must not change between
- * create and the runs (both caches depend on them; violating this gives
- * unspecified results but stays memory-safe); out capacities must fit the
+ * re-searching.  A batch that runs intersect or difference builds a THIRD
+ * cache ahead of its first such run: a 32-bit tile-major copy of its inputs
+ * (one 8208-byte record per tile, about 4 B per input element, device).
+ * Tiles whose elements all share their upper 32 bits (decided from the
+ * data, per tile) are then filled and walked from that copy at half the
+ * bytes; every other tile, and union, reads the lists as before.  The
+ * allocation is tried once; if it fails, or with UA_NARROW=0 in the
+ * environment, the batch runs without it.  ua_batch_info reports it.
+ * All three caches rest on the same promise: the pairs' device contents must
+ * not change between create and the runs (violating this gives unspecified
+ * results but stays memory-safe); out capacities must fit the
  * op (intersect >= min(n,m), merge >= n+m, difference >= n). */
 typedef struct ua_batch ua_batch;
 enum { UA_OP_INTERSECT = 0, UA_OP_MERGE = 1, UA_OP_DIFFERENCE = 2 };
@@ -158,6 +166,12 @@ int ua_batch_run(ua_ctx *, ua_batch *, int op, uint64_t *out_lens);
 int ua_batch_run_n(ua_ctx *, ua_batch *, int op, int n_runs,
                    uint64_t *out_lens);
 void ua_batch_destroy(ua_ctx *, ua_batch *);
+/* What the batch holds (any out pointer may be NULL): its tile count, how
+ * many of the tiles run from the 32-bit copy, and that cache's device bytes.
+ * Both are 0 until the first intersect/difference run has built the cache,
+ * and stay 0 when it is disabled or could not be allocated.  (since v13) */
+int ua_batch_info(ua_ctx *, ua_batch *, uint64_t *tiles, uint64_t *narrow_tiles,
+                  uint64_t *narrow_bytes);
 /* batched pairwise algo.MergeSorted semantics (dedup union, uidlist.go:448) */
 int ua_merge_batch_dev(ua_ctx *, const ua_dpair *pairs, int n_pairs,
                        uint64_t *out_lens);
