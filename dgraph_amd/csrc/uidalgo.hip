@@ -243,8 +243,14 @@ __device__ __forceinline__ void d_block_scan(int tid, u32 cnt, u32 *wsum,
  * duplicates WITHIN one list (TestMergeSorted6/9/10).  Rule: emit iff value
  * != previous emitted value == previous merged-stream value.  A thread's
  * initial "previous" is max(last A before it, last B before it), using the
- * staged tile-boundary elements when its segment starts at a range head. */
-template <int OP, int W>
+ * staged tile-boundary elements when its segment starts at a range head.
+ *
+ * VALUES = false is the COUNT-only walk: MODE_COUNT needs only the per-thread
+ * emission count (union's first pass; intersect and difference never run a
+ * count pass), so the em[] and flags bookkeeping is dropped (flags = 0, em
+ * untouched).  The dedup state is the same code, so union counts match the
+ * value walk exactly. */
+template <int OP, bool VALUES, int W>
 __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int alen,
                                           int boff, int blen, u64 a_before, bool has_ab,
                                           u64 b_before, bool has_bb,
@@ -290,74 +296,14 @@ __device__ __forceinline__ int tile_walk2(const u64 *smembase, int aoff, int ale
             prev_out = val;
             has_prev = true;
         }
-        em[s] = val;
-        flags |= ((u32)emit) << s;
-        cnt += emit;
-        int ni = i + (takeA ? 1 : 0);
-        int nj = j + (takeA ? 0 : 1);
-        /* one refill: next lookahead of the consumed side */
-        int ra = (ni + 1) < alen ? (ni + 1) : amax;
-        int rb = (nj + 1) < blen_ext ? (nj + 1) : bmax;
-        int raddr = takeA ? (aoff + ra) : (boff + rb);
-        u64 r = smembase[raddr];
-        a = takeA ? an : a;
-        b = takeA ? b : bn;
-        an = takeA ? r : an;
-        bn = takeA ? bn : r;
-        i = ni;
-        j = nj;
-    }
-    return cnt;
-}
-
-/* COUNT-only walk: tile_walk2 minus the em[] value writes — MODE_COUNT
- * needs only the per-thread emission count (union's first pass; intersect
- * and difference never run a count pass).  Dedup state is kept so union
- * counts match tile_walk2 exactly. */
-template <int OP, int W>
-__device__ __forceinline__ int tile_walk2c(const u64 *smembase, int aoff, int alen,
-                                           int boff, int blen, u64 a_before,
-                                           bool has_ab, u64 b_before, bool has_bb,
-                                           bool has_bn, int s0, int s1, int i0) {
-    static_assert(OP == OP_UNION || OP == OP_MERGE_ALL,
-                  "intersect/difference take tile_walk3x");
-    int i = i0, j = s0 - i0;
-    int cnt = 0;
-    int steps = s1 - s0;
-    int blen_ext = blen + (has_bn ? 1 : 0);
-    int amax = alen > 0 ? alen - 1 : 0;
-    int bmax = blen_ext > 0 ? blen_ext - 1 : 0;
-    u64 a = smembase[aoff + (i < alen ? i : amax)];
-    u64 an = smembase[aoff + ((i + 1) < alen ? (i + 1) : amax)];
-    u64 b = smembase[boff + (j < blen_ext ? j : bmax)];
-    u64 bn = smembase[boff + ((j + 1) < blen_ext ? (j + 1) : bmax)];
-    bool has_prev = false;
-    u64 prev_out = 0;
-    if (OP == OP_UNION) {
-        u64 pa = (i > 0) ? smembase[aoff + i - 1] : a_before;
-        bool hpa = (i > 0) || has_ab;
-        u64 pb = (j > 0) ? smembase[boff + j - 1] : b_before;
-        bool hpb = (j > 0) || has_bb;
-        has_prev = hpa || hpb;
-        prev_out = !hpa ? pb : (!hpb ? pa : (pa > pb ? pa : pb));
-    }
-#pragma unroll
-    for (int s = 0; s < W; s++) {
-        if (s >= steps) break;
-        bool inA = i < alen, inB = j < blen;
-        if (!inA && !inB) break;
-        bool takeA = inA && (!inB || a <= b);
-        bool emit;
-        if (OP == OP_MERGE_ALL) emit = true;
-        else {
-            u64 val = takeA ? a : b;
-            emit = !has_prev || val != prev_out;
-            prev_out = val;
-            has_prev = true;
+        if constexpr (VALUES) {
+            em[s] = val;
+            flags |= ((u32)emit) << s;
         }
         cnt += emit;
         int ni = i + (takeA ? 1 : 0);
         int nj = j + (takeA ? 0 : 1);
+        /* one refill: next lookahead of the consumed side */
         int ra = (ni + 1) < alen ? (ni + 1) : amax;
         int rb = (nj + 1) < blen_ext ? (nj + 1) : bmax;
         int raddr = takeA ? (aoff + ra) : (boff + rb);
@@ -407,42 +353,41 @@ __device__ __forceinline__ int tile_walk3x(const E *smembase, int aoff, int alen
     flags = 0;
     amA = 0;
     amB = 0;
+    /* One merge step of one chain: its frontier (a, b) at (i, j), its takeA
+     * mask, and where its emission bits start in flags.  The form is load-
+     * bearing: the tile's constants are captured by value and the chain's
+     * state is copied to locals before the test, so that the step is
+     * simplified on plain values before it is inlined, as the spelled-out
+     * step was.  With by-reference captures, or with the test reading i and j
+     * through their references, the same source compiles to a longer loop
+     * (profiles/tile_refactor.md). */
+    auto step = [=, &flags, &cnt](int q, int steps, E &a, E &b, int &i, int &j, u32 &mask,
+                                  int fshift) __attribute__((always_inline)) {
+        const int ci = i, cj = j;
+        const E ca = a, cb = b;
+        if (q < steps && (ci < alen || cj < blen)) {
+            bool inA = ci < alen, inB = cj < blen;
+            bool takeA = inA && (!inB || ca <= cb);
+            bool eq = (ca == cb) && (cj < blen_ext);
+            bool emit = (OP == OP_INTERSECT) ? (takeA && eq) : (takeA && !eq);
+            flags |= ((u32)emit) << (fshift + q);
+            mask |= ((u32)takeA) << q;
+            cnt += emit;
+            int ni = ci + (takeA ? 1 : 0), nj = cj + (takeA ? 0 : 1);
+            int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
+                              : (boff + (nj < blen_ext ? nj : bmax));
+            E r = smembase[raddr];
+            a = takeA ? r : ca;
+            b = takeA ? cb : r;
+            i = ni;
+            j = nj;
+        }
+    };
+    /* A's step, then B's: the two gather chains stay interleaved */
 #pragma unroll
     for (int q = 0; q < H; q++) {
-        if (q < stepsA && (ia < alen || ja < blen)) {
-            bool inA = ia < alen, inB = ja < blen;
-            bool takeA = inA && (!inB || aA <= bA);
-            bool eq = (aA == bA) && (ja < blen_ext);
-            bool emit = (OP == OP_INTERSECT) ? (takeA && eq) : (takeA && !eq);
-            flags |= ((u32)emit) << q;
-            amA |= ((u32)takeA) << q;
-            cnt += emit;
-            int ni = ia + (takeA ? 1 : 0), nj = ja + (takeA ? 0 : 1);
-            int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
-                              : (boff + (nj < blen_ext ? nj : bmax));
-            E r = smembase[raddr];
-            aA = takeA ? r : aA;
-            bA = takeA ? bA : r;
-            ia = ni;
-            ja = nj;
-        }
-        if (q < stepsB && (ib < alen || jb < blen)) {
-            bool inA = ib < alen, inB = jb < blen;
-            bool takeA = inA && (!inB || aB <= bB);
-            bool eq = (aB == bB) && (jb < blen_ext);
-            bool emit = (OP == OP_INTERSECT) ? (takeA && eq) : (takeA && !eq);
-            flags |= ((u32)emit) << (H + q);
-            amB |= ((u32)takeA) << q;
-            cnt += emit;
-            int ni = ib + (takeA ? 1 : 0), nj = jb + (takeA ? 0 : 1);
-            int raddr = takeA ? (aoff + (ni < alen ? ni : amax))
-                              : (boff + (nj < blen_ext ? nj : bmax));
-            E r = smembase[raddr];
-            aB = takeA ? r : aB;
-            bB = takeA ? bB : r;
-            ib = ni;
-            jb = nj;
-        }
+        step(q, stepsA, aA, bA, ia, ja, amA, 0);
+        step(q, stepsB, aB, bB, ib, jb, amB, H);
     }
     return cnt;
 }
@@ -464,6 +409,131 @@ __device__ __forceinline__ u64 *d_stage_dst(u64 t, int tid, u32 cnt, u32 excl, u
     if (prim) dst += excl;
     if (tid == 0) tile_cnt[t] = total < (u32)stage_stride ? total : (u32)stage_stride;
     return dst;
+}
+
+/* The consumer side of the same rule: where the compactors (k_compact_small,
+ * k_compact, k_tail_fused) find the cnt = tile_cnt[t] values that
+ * d_stage_dst placed for tile t.  prim is the dense primary region, or null
+ * when the batch has none. */
+__device__ __forceinline__ const u64 *d_stage_src(u64 t, u32 cnt,
+                                                  const u64 *__restrict__ staging,
+                                                  u64 stage_stride,
+                                                  const u64 *__restrict__ prim) {
+    return (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
+                                            : staging + t * stage_stride;
+}
+
+/* A pair's output capacity: the most a valid pair can emit, and so the size
+ * its out buffer is promised to have.  Every compactor clamps to it: invalid
+ * (duplicate/unsorted) inputs can emit more and must stay memory-safe, like
+ * the reference. */
+__device__ __forceinline__ u64 d_pair_cap(const UaDesc &d, int op) {
+    return (op == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
+           : (op == OP_DIFF)    ? d.n
+                                : (d.n + d.m);
+}
+
+/* ==================== tile geometry, splits, write-back ====================
+ * One copy of what k_narrow (which builds a tile's record), tile_narrow and
+ * tile_wide (which walk it) and the split cache (producer and consumer) have
+ * to agree on bit for bit. */
+
+/* A tile's ranges: A = d.u[a0, a0 + alen), B = d.v[b0, b1) with blen = b1 - b0,
+ * from merge-path diagonal d0.  has_bn: B's lookahead d.v[b1] exists.  t/tn,
+ * p/pn, a0/a0n are the tile's and its (clamped) neighbour's index, pair and
+ * partition word: the A range ends where the next tile of the same pair
+ * starts, else at the list's end. */
+struct UaTileGeom {
+    u64 d0;
+    u32 b0, b1;
+    int alen, blen;
+    bool has_bn;
+};
+
+__device__ __forceinline__ UaTileGeom d_tile_geom(const UaDesc &d, u64 t, u64 tn, u32 p,
+                                                  u32 pn, u32 a0, u32 a0n) {
+    UaTileGeom g;
+    u64 lt = t - d.tile_base;
+    u64 path = d.n + d.m;
+    g.d0 = lt * UA_TILE;
+    if (g.d0 > path) g.d0 = path; /* capacity-tiled batches can overshoot the path */
+    u64 d1 = g.d0 + UA_TILE;
+    if (d1 > path) d1 = path;
+    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
+    g.b0 = (u32)(g.d0 - a0);
+    g.b1 = (u32)(d1 - a1);
+    g.alen = (int)(a1 - a0);
+    g.blen = (int)(g.b1 - g.b0);
+    g.has_bn = ((u64)g.b1 < d.m);
+    return g;
+}
+
+/* A thread's merge-path segment [s0, s1) of the tile, cut at smid into the
+ * two chains of tile_walk3x; all three clamped to the tile's length. */
+struct UaSeg {
+    int s0, smid, s1;
+};
+
+__device__ __forceinline__ UaSeg d_thread_seg(int tid, int tilelen) {
+    UaSeg sg;
+    sg.s0 = tid * UA_WPT;
+    sg.s1 = sg.s0 + UA_WPT;
+    if (sg.s0 > tilelen) sg.s0 = tilelen;
+    if (sg.s1 > tilelen) sg.s1 = tilelen;
+    sg.smid = sg.s0 + UA_WPT / 2;
+    if (sg.smid > tilelen) sg.smid = tilelen;
+    if (sg.smid < sg.s0) sg.smid = sg.s0;
+    if (sg.smid > sg.s1) sg.smid = sg.s1;
+    return sg;
+}
+
+/* The thread's splits: i0 = #A consumed at diagonal s0, i0b at smid.  From the
+ * cached word split_w when the batch has one (PACKED lo16 = i0, hi16 = i0b),
+ * else by two searches of the tile in LDS; stored in the same format when
+ * isplit_out is set.  Called below the fill's barrier: the opaque pin here is
+ * the first use of split_w, which was the tile's first vector load, so that no
+ * wait stands between that load and the fill behind it. */
+struct UaSplit {
+    int i0, i0b;
+};
+
+template <typename E>
+__device__ __forceinline__ UaSplit d_resolve_splits(const E *lds, int aoff, int alen, int boff,
+                                                    int blen, UaSeg sg, bool have_split,
+                                                    u32 split_w, u32 *__restrict__ isplit_out,
+                                                    u64 t, int tid) {
+    UaSplit sp;
+    if (have_split) {
+        asm volatile("" : "+v"(split_w));
+        sp.i0 = (int)(split_w & 0xffffu);
+        sp.i0b = (int)(split_w >> 16);
+    } else {
+        sp.i0 = d_merge_path_tile(lds, aoff, alen, boff, blen, sg.s0);
+        sp.i0b = d_merge_path_tile(lds, aoff, alen, boff, blen, sg.smid);
+    }
+    if (isplit_out) isplit_out[t * UA_TBLOCK + tid] = (u32)sp.i0 | ((u32)sp.i0b << 16);
+    return sp;
+}
+
+/* Write-back of tile_walk3x: the emitted A-values are rebuilt from the
+ * per-chain takeA masks (A-index at step s = the chain's split + popcount of
+ * its mask below s) and read from As, the tile's A range in LDS; at most lim
+ * of them go to dst.  A narrow tile (E = u32) gets its common high half hi64
+ * back on the way; the 64-bit path has no OR. */
+template <typename E>
+__device__ __forceinline__ void d_write_a_only(const E *As, u32 flags, u32 amA, u32 amB,
+                                               UaSplit sp, u32 lim, u64 *dst, u64 hi64) {
+    constexpr int H = UA_WPT / 2;
+    u32 f = flags;
+    u32 k = 0;
+    while (f && k < lim) {
+        int s = __builtin_ctz(f);
+        f &= f - 1;
+        int idx = (s < H) ? sp.i0 + __popc(amA & ((1u << s) - 1))
+                          : sp.i0b + __popc(amB & ((1u << (s - H)) - 1));
+        if constexpr (sizeof(E) == 8) dst[k++] = As[idx];
+        else dst[k++] = hi64 | As[idx];
+    }
 }
 
 /* ==================== narrow tiles (prepared batches) ====================
@@ -517,17 +587,10 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
     u32 a0 = tile_a0[t];
     u32 a0n = tile_a0[tn];
     UaDesc d = descs[p];
-    /* the tile's ranges, exactly as k_tiles derives them */
-    u64 lt = t - d.tile_base;
-    u64 path = d.n + d.m;
-    u64 d0 = lt * UA_TILE;
-    if (d0 > path) d0 = path;
-    u64 d1 = d0 + UA_TILE;
-    if (d1 > path) d1 = path;
-    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
-    u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
-    int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
-    bool has_bn = ((u64)b1 < d.m);
+    const UaTileGeom g = d_tile_geom(d, t, tn, p, pn, a0, a0n);
+    const u32 b0 = g.b0, b1 = g.b1;
+    const int alen = g.alen, blen = g.blen;
+    const bool has_bn = g.has_bn;
     bool sane = alen >= 0 && blen >= 0 && alen + blen >= 1 && alen + blen <= UA_TILE &&
                 (u64)a0 + (u64)alen <= d.n && (u64)b0 + (u64)blen <= d.m;
     u32 *rec = slab + t * UA_NREC_W;
@@ -575,20 +638,125 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
     }
 }
 
+/* tile LDS + two boundary slots (union's a_before / b_before) */
+constexpr int UA_SLOT_AB = UA_SMEMN, UA_SLOT_BB = UA_SMEMN + 1;
+constexpr int UA_TILE_LDS = UA_SMEMN + 2; /* u64 */
+
+/* the fill's cache policy (see UA_FILL_NT) */
+constexpr bool d_fill_nt(int op) { return (UA_FILL_NT != 0) && (op == OP_INTERSECT); }
+
+/* perf-bisection builds (UA_ABLATE): the stages they cut, named once */
+constexpr bool UA_DO_FILL = (UA_ABLATE != 2);
+constexpr bool UA_DO_WALK = (UA_ABLATE != 1);
+constexpr bool UA_DO_EMIT = (UA_ABLATE != 3);
+
+/* Everything behind the fill's barrier, for both tile bodies: the thread's
+ * segment and splits, the walk, the block scan and the write-back.  lds holds
+ * the tile as E (u64, or u32 on a narrow tile): A at aoff, B at boff with its
+ * lookahead as element blen when has_bn, and for union the two boundary
+ * slots.  hi64 is a narrow tile's common high half (unused when E = u64). */
+template <int OP, int MODE, typename E>
+__device__ __forceinline__ void tile_finish(
+    const E *lds, int aoff, int alen, int boff, int blen, bool has_ab, bool has_bb,
+    bool has_bn, u64 hi64, const UaDesc &d, u64 d0, u64 t, u32 *scan,
+    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
+    const u64 *__restrict__ offs, const u64 *__restrict__ partials, bool have_split,
+    u32 split_w, u32 *__restrict__ isplit_out) {
+    /* intersect/difference emit A-values only: maskless walk, values rebuilt
+     * from LDS at write-back; union/merge-all carry them in em[] */
+    constexpr bool A_ONLY = (OP == OP_INTERSECT || OP == OP_DIFF);
+    int tid = threadIdx.x;
+    u64 em[UA_WPT];
+    u32 flags = 0;
+    u32 amA = 0, amB = 0; /* walk3x: per-chain takeA bits for reconstruction */
+    UaSplit sp = {0, 0};
+    int cnt = 0;
+    if constexpr (!UA_DO_WALK) { /* fill-only: keep the loads live, skip search+walk */
+        E ablate_x = lds[aoff + tid] + lds[boff + (tid & 127)];
+        asm volatile("" ::"v"(ablate_x));
+    } else {
+        UaSeg sg = d_thread_seg(tid, alen + blen);
+        sp = d_resolve_splits(lds, aoff, alen, boff, blen, sg, have_split, split_w,
+                              isplit_out, t, tid);
+        if constexpr (A_ONLY) {
+            cnt = tile_walk3x<OP, UA_WPT>(lds, aoff, alen, boff, blen, has_bn, sg.s0, sg.smid,
+                                          sg.s1, sp.i0, sp.i0b, flags, amA, amB);
+        } else {
+            u64 a_before = 0, b_before = 0;
+            if constexpr (OP == OP_UNION) {
+                a_before = lds[UA_SLOT_AB];
+                b_before = lds[UA_SLOT_BB];
+            }
+            /* the count pass needs no values — no em[] bookkeeping */
+            cnt = tile_walk2<OP, MODE != MODE_COUNT>(lds, aoff, alen, boff, blen, a_before,
+                                                     has_ab, b_before, has_bb, has_bn, sg.s0,
+                                                     sg.s1, sp.i0, em, flags);
+        }
+        if constexpr (MODE == MODE_DIRECT) {
+            /* OP_MERGE_ALL: every path element emits, so the output position
+             * IS the path position — no scan, no staging, no compaction */
+            u64 *dst = d.out + d0 + (u64)sg.s0;
+            int steps = sg.s1 - sg.s0;
+#pragma unroll
+            for (int s = 0; s < UA_WPT; s++) {
+                if (s < steps) dst[s] = em[s];
+            }
+            return;
+        }
+    }
+    if constexpr (!UA_DO_EMIT) { /* fill+walk, skip scan/write-back */
+        asm volatile("" ::"v"(cnt), "v"(flags));
+        cnt = 0;
+        flags = 0;
+    }
+
+    u32 excl, total;
+    d_block_scan<UA_TBLOCK>(tid, (u32)cnt, scan, excl, total);
+
+    if (MODE == MODE_COUNT) {
+        if (tid == 0) tile_cnt[t] = total;
+        return;
+    }
+    u64 *dst;
+    u32 lim = (u32)cnt;
+    if (MODE == MODE_STAGE) {
+        /* offs = the dense primary region's base, see enqueue_tiles */
+        dst = d_stage_dst(t, tid, (u32)cnt, excl, total, staging, stage_stride, offs,
+                          tile_cnt, lim);
+    } else { /* MODE_WRITE: (offs, partials) is the split flat scan */
+        dst = d.out +
+              (d_off(offs, partials, t) - d_off(offs, partials, d.tile_base)) + excl;
+    }
+    if (cnt > 0) {
+        if constexpr (A_ONLY) {
+            d_write_a_only(lds + aoff, flags, amA, amB, sp, lim, dst, hi64);
+        } else {
+            u32 k = 0;
+#pragma unroll
+            for (int s = 0; s < UA_WPT; s++) {
+                if (flags & (1u << s)) {
+                    if (k < lim) dst[k] = em[s];
+                    k++;
+                }
+            }
+        }
+    }
+}
+
 /* One narrow tile of k_tiles<OP_INTERSECT | OP_DIFF, MODE_STAGE>: the record
  * goes to LDS by LDS-DMA as soon as t is known (its address needs no
  * descriptor), descs[p] arrives behind it, and the walk runs on u32.  Indices,
  * clamps, masks, the cached split format, the scan and the staging are the
- * wide path's; emitted A-values get the tile's high half back on the way to
- * staging. */
+ * wide path's (tile_finish); emitted A-values get the tile's high half back on
+ * the way to staging. */
 template <int OP>
 __device__ __forceinline__ void tile_narrow(
     const UaDesc *__restrict__ descs, u32 p, u32 pn, u32 a0, u32 a0n, u64 t, u64 tn,
     const u32 *__restrict__ slab, u64 *smem, u32 *scan, u64 *__restrict__ staging,
     u64 stage_stride, u32 *__restrict__ tile_cnt, const u64 *__restrict__ primary,
     const u32 *__restrict__ isplit_in, u32 *__restrict__ isplit_out) {
-    constexpr bool FILL_NT = (UA_FILL_NT != 0) && (OP == OP_INTERSECT);
-    constexpr int FILL_AUX = FILL_NT ? 2 : 0;
+    constexpr bool FILL_NT = d_fill_nt(OP);
+    constexpr int FILL_AUX = FILL_NT ? 2 : 0; /* 2 = nt for global_load_lds */
     int tid = threadIdx.x;
     /* cached splits: still the first vector load, opaque until the barrier */
     const bool have_split = (isplit_in != nullptr);
@@ -597,8 +765,7 @@ __device__ __forceinline__ void tile_narrow(
     u32 *s32 = (u32 *)smem;
     const u32 *rec = slab + t * UA_NREC_W;
     u32x4 tl = {0, 0, 0, 0}; /* the record's tail: high half, lookahead, 0, 0 */
-#if UA_ABLATE != 2
-    {
+    if constexpr (UA_DO_FILL) {
         int wv4 = tid >> 6, lane = tid & 63;
 #pragma unroll
         for (int r = 0; r < UA_NROUNDS; r++) {
@@ -613,142 +780,42 @@ __device__ __forceinline__ void tile_narrow(
         if constexpr (FILL_NT) tl = __builtin_nontemporal_load(tp);
         else tl = *tp;
     }
-#endif
     UaDesc d = descs[p];
-    u64 lt = t - d.tile_base;
-    u64 path = d.n + d.m;
-    u64 d0 = lt * UA_TILE;
-    if (d0 > path) d0 = path;
-    u64 d1 = d0 + UA_TILE;
-    if (d1 > path) d1 = path;
-    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
-    u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
-    int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
-    bool has_bn = ((u64)b1 < d.m);
+    const UaTileGeom g = d_tile_geom(d, t, tn, p, pn, a0, a0n);
     constexpr int aoff = 0;
-    int boff = alen;
-#if UA_ABLATE != 2
-    /* the one drain (see the wide fill); all four tail words pass through
-     * it, so no register of the load is reused, and waited for, earlier */
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(tl)::"memory");
-    if (tid == 0) s32[boff + blen] = tl.y; /* B's lookahead, element blen of B */
-#endif
-    const u32 hiw = tl.x;
+    int boff = g.alen;
+    if constexpr (UA_DO_FILL) {
+        /* the one drain (see the wide fill); all four tail words pass through
+         * it, so no register of the load is reused, and waited for, earlier */
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(tl)::"memory");
+        if (tid == 0) s32[boff + g.blen] = tl.y; /* B's lookahead, element blen of B */
+    }
+    const u64 hi64 = (u64)tl.x << 32;
     __syncthreads();
-
-    u32 flags;
-    u32 amA = 0, amB = 0;
-    int w_i0 = 0, w_i0b = 0;
-    int cnt;
-#if UA_ABLATE == 1 /* fill-only */
-    u32 ablate_x = s32[tid] + s32[UA_TILE / 2 + tid];
-    asm volatile("" ::"v"(ablate_x));
-    flags = 0;
-    cnt = 0;
-    (void)split_w; (void)have_split; (void)has_bn; (void)isplit_out; (void)boff;
-#else
-    int tilelen = alen + blen;
-    int s0 = tid * UA_WPT;
-    int s1 = s0 + UA_WPT;
-    if (s0 > tilelen) s0 = tilelen;
-    if (s1 > tilelen) s1 = tilelen;
-    int smid = s0 + UA_WPT / 2;
-    if (smid > tilelen) smid = tilelen;
-    if (smid < s0) smid = s0;
-    if (smid > s1) smid = s1;
-    if (have_split) {
-        asm volatile("" : "+v"(split_w));
-        w_i0 = (int)(split_w & 0xffffu);
-        w_i0b = (int)(split_w >> 16);
-    } else {
-        w_i0 = d_merge_path_tile(s32, aoff, alen, boff, blen, s0);
-        w_i0b = d_merge_path_tile(s32, aoff, alen, boff, blen, smid);
-    }
-    if (isplit_out) isplit_out[t * UA_TBLOCK + tid] = (u32)w_i0 | ((u32)w_i0b << 16);
-    cnt = tile_walk3x<OP, UA_WPT>(s32, aoff, alen, boff, blen, has_bn, s0, smid, s1, w_i0,
-                                  w_i0b, flags, amA, amB);
-#endif
-#if UA_ABLATE == 3 /* fill+walk, skip scan/write-back */
-    asm volatile("" ::"v"(cnt), "v"(flags));
-    cnt = 0;
-    flags = 0;
-#endif
-    u32 excl, total;
-    d_block_scan<UA_TBLOCK>(tid, (u32)cnt, scan, excl, total);
-    u32 lim;
-    u64 *dst = d_stage_dst(t, tid, (u32)cnt, excl, total, staging, stage_stride, primary,
-                           tile_cnt, lim);
-    if (cnt > 0) {
-        constexpr int H = UA_WPT / 2;
-        u64 hi64 = (u64)hiw << 32;
-        u32 f = flags;
-        u32 k = 0;
-        while (f && k < lim) {
-            int s = __builtin_ctz(f);
-            f &= f - 1;
-            int idx = (s < H) ? w_i0 + __popc(amA & ((1u << s) - 1))
-                              : w_i0b + __popc(amB & ((1u << (s - H)) - 1));
-            dst[k++] = hi64 | s32[aoff + idx];
-        }
-    }
+    tile_finish<OP, MODE_STAGE>(s32, aoff, g.alen, boff, g.blen, false, false, g.has_bn, hi64,
+                                d, g.d0, t, scan, staging, stage_stride, tile_cnt, primary,
+                                nullptr, have_split, split_w, isplit_out);
 }
 
+/* One 64-bit tile of k_tiles: every op and mode, and every tile that is not
+ * narrow. */
 template <int OP, int MODE>
-__global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
-    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
-    const u32 *__restrict__ tile_a0, u64 total_tiles,
-    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
-    const u64 *__restrict__ offs, const u64 *__restrict__ partials /* MODE_WRITE only */,
-    const u32 *__restrict__ isplit_in /* cached per-thread merge-path splits,
-        PACKED lo16 = i0 at diagonal s0, hi16 = i0b at smid (prepared batch:
-        inputs immutable, so splits are run-invariant like the tile
-        partition); null = compute */,
-    u32 *__restrict__ isplit_out /* store packed splits on the first run */,
-    const u32 *__restrict__ slab /* prepared batch's narrow records (then
-        tile_pair is its private copy with UA_NARROW_BIT), or null */) {
-    /* tile LDS + two boundary slots (union's a_before / b_before) */
-    __shared__ __align__(16) u64 smem[UA_SMEMN + 2];
-    __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
-    constexpr int SLOT_AB = UA_SMEMN, SLOT_BB = UA_SMEMN + 1;
-    /* the fill's cache policy (see UA_FILL_NT); 2 = nt for global_load_lds */
-    constexpr bool FILL_NT = (UA_FILL_NT != 0) && (OP == OP_INTERSECT);
-    constexpr int FILL_AUX = FILL_NT ? 2 : 0;
-
-    u64 t = blockIdx.x;
+__device__ __forceinline__ void tile_wide(
+    const UaDesc *__restrict__ descs, u32 p, u32 pn, u32 a0, u32 a0n, u64 t, u64 tn,
+    u64 *smem, u32 *scan, u64 *__restrict__ staging, u64 stage_stride,
+    u32 *__restrict__ tile_cnt, const u64 *__restrict__ offs,
+    const u64 *__restrict__ partials, const u32 *__restrict__ isplit_in,
+    u32 *__restrict__ isplit_out) {
+    constexpr bool FILL_NT = d_fill_nt(OP);
+    constexpr int FILL_AUX = FILL_NT ? 2 : 0; /* 2 = nt for global_load_lds */
     int tid = threadIdx.x;
-    /* all four tile words are requested together (one scalar round trip);
-     * the neighbour index is clamped, not branched on, so nothing past the
-     * arrays is read and no load waits on another's result */
-    u64 tn = (t + 1 < total_tiles) ? t + 1 : t;
-    u32 p = tile_pair[t];
-    u32 pn = tile_pair[tn];
-    u32 a0 = tile_a0[t];
-    u32 a0n = tile_a0[tn];
-    if constexpr ((OP == OP_INTERSECT || OP == OP_DIFF) && MODE == MODE_STAGE) {
-        /* eligibility rides in the first scalar round trip: nothing new
-         * stands between it and the fill */
-        const bool narrow = (slab != nullptr) && (p & UA_NARROW_BIT);
-        p &= ~UA_NARROW_BIT;
-        pn &= ~UA_NARROW_BIT;
-        if (narrow) {
-            tile_narrow<OP>(descs, p, pn, a0, a0n, t, tn, slab, smem, scan, staging,
-                            stage_stride, tile_cnt, offs, isplit_in, isplit_out);
-            return;
-        }
-    }
     UaDesc d = descs[p];
-    u64 lt = t - d.tile_base;
-    u64 path = d.n + d.m;
-    u64 d0 = lt * UA_TILE;
-    if (d0 > path) d0 = path; /* capacity-tiled batches can overshoot the path */
-    u64 d1 = d0 + UA_TILE;
-    if (d1 > path) d1 = path;
-    u32 a1 = (tn != t && pn == p) ? a0n : (u32)d.n;
-    u32 b0 = (u32)(d0 - a0), b1 = (u32)(d1 - a1);
-    int alen = (int)(a1 - a0), blen = (int)(b1 - b0);
+    const UaTileGeom tg = d_tile_geom(d, t, tn, p, pn, a0, a0n);
+    const u32 b0 = tg.b0;
+    const int alen = tg.alen, blen = tg.blen;
     /* cached splits: the first vector load of the tile.  The word stays
-     * opaque (split_w is pinned below the barrier) so that no wait stands
-     * between this load and the fill behind it */
+     * opaque (d_resolve_splits pins it below the barrier) so that no wait
+     * stands between this load and the fill behind it */
     const bool have_split = (isplit_in != nullptr);
     u32 split_w = 0;
     if (have_split) split_w = isplit_in[t * UA_TBLOCK + tid];
@@ -769,14 +836,12 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
 
     bool has_ab = (a0 > 0);
     bool has_bb = (b0 > 0);
-    bool has_bn = ((u64)b1 < d.m);
-#if UA_ABLATE == 5 /* meta + dispatch floor: no fill, no walk, no scan */
-    if (tid == 0) tile_cnt[t] = (u32)((a0 ^ (u32)d.m) & 1u);
-    (void)has_ab; (void)has_bb; (void)has_bn; (void)split_w;
-    return;
-#endif
-#if UA_ABLATE != 2
-    {
+    bool has_bn = tg.has_bn;
+    if constexpr (UA_ABLATE == 5) { /* meta + dispatch floor: no fill, no walk, no scan */
+        if (tid == 0) tile_cnt[t] = (u32)((a0 ^ (u32)d.m) & 1u);
+        return;
+    }
+    if constexpr (UA_DO_FILL) {
         /* Issue everything, wait once.  Per-wave LDS-DMA bodies (128 u64 per
          * wave-call: 64 lanes x 16 B) for A and B, then each side's
          * remainder (< 128 elements: one predicated load per thread) and the
@@ -821,10 +886,10 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         } else if (tid == 1) {
             if (bhead) { xsrc = d.v + b0; xslot = boff; }
         } else if (OP == OP_UNION && tid == 2) {
-            xslot = SLOT_AB;
+            xslot = UA_SLOT_AB;
             if (has_ab) xsrc = d.u + a0 - 1;
         } else if (OP == OP_UNION && tid == 3) {
-            xslot = SLOT_BB;
+            xslot = UA_SLOT_BB;
             if (has_bb) xsrc = d.v + b0 - 1;
         }
         u64 rx = 0;
@@ -838,126 +903,50 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
         if (ib <= blen) Bs[ib] = rb;
         if (xslot >= 0) smem[xslot] = rx;
     }
-#endif
     __syncthreads();
+    tile_finish<OP, MODE>(smem, aoff, alen, boff, blen, has_ab, has_bb, has_bn, 0, d, tg.d0, t,
+                          scan, staging, stage_stride, tile_cnt, offs, partials, have_split,
+                          split_w, isplit_out);
+}
 
-    /* intersect/difference emit A-values only: maskless walk, values rebuilt
-     * from LDS at write-back; union/merge-all carry them in em[] */
-    constexpr bool A_ONLY = (OP == OP_INTERSECT || OP == OP_DIFF);
-#if UA_ABLATE == 1 /* fill-only: keep the loads live, skip search+walk */
-    u64 ablate_x = smem[aoff + tid] + smem[boff + (tid & 127)];
-    asm volatile("" ::"v"(ablate_x));
-    u64 em[UA_WPT];
-    u32 flags = 0;
-    u32 amA = 0, amB = 0;
-    int w_i0 = 0, w_i0b = 0;
-    int cnt = 0;
-    (void)split_w; (void)have_split;
-#else
-    u64 em[UA_WPT];
-    u32 flags;
-    u32 amA = 0, amB = 0; /* walk3x: per-chain takeA bits for reconstruction */
-    int w_i0 = 0, w_i0b = 0;
-    int cnt;
-    int tilelen = alen + blen;
-    int s0 = tid * UA_WPT;
-    int s1 = s0 + UA_WPT;
-    if (s0 > tilelen) s0 = tilelen;
-    if (s1 > tilelen) s1 = tilelen;
-    int smid = s0 + UA_WPT / 2;
-    if (smid > tilelen) smid = tilelen;
-    if (smid < s0) smid = s0;
-    if (smid > s1) smid = s1;
-    int i0, i0b;
-    if (have_split) {
-        /* first use of the cached word, pinned below the barrier */
-        asm volatile("" : "+v"(split_w));
-        i0 = (int)(split_w & 0xffffu);
-        i0b = (int)(split_w >> 16);
-    } else {
-        i0 = d_merge_path_tile(smem, aoff, alen, boff, blen, s0);
-        i0b = d_merge_path_tile(smem, aoff, alen, boff, blen, smid);
-    }
-    if (isplit_out)
-        isplit_out[t * UA_TBLOCK + tid] = (u32)i0 | ((u32)i0b << 16);
-    u64 a_before = (OP == OP_UNION) ? smem[SLOT_AB] : 0;
-    u64 b_before = (OP == OP_UNION) ? smem[SLOT_BB] : 0;
-    if constexpr (A_ONLY) {
-        cnt = tile_walk3x<OP, UA_WPT>(smem, aoff, alen, boff, blen, has_bn,
-                                      s0, smid, s1, i0, i0b, flags, amA, amB);
-        w_i0 = i0;
-        w_i0b = i0b;
-    } else if constexpr (MODE == MODE_COUNT) {
-        /* count pass needs no values — skip the em[] bookkeeping */
-        cnt = tile_walk2c<OP, UA_WPT>(smem, aoff, alen, boff, blen, a_before,
-                                      has_ab, b_before, has_bb, has_bn, s0, s1,
-                                      i0);
-        flags = 0;
-    } else {
-        cnt = tile_walk2<OP>(smem, aoff, alen, boff, blen,
-                             a_before, has_ab, b_before, has_bb, has_bn, s0, s1,
-                             i0, em, flags);
-    }
-    if (MODE == MODE_DIRECT) {
-        /* OP_MERGE_ALL: every path element emits, so the output position
-         * IS the path position — no scan, no staging, no compaction */
-        u64 *dst = d.out + d0 + (u64)s0;
-        int steps = s1 - s0;
-#pragma unroll
-        for (int s = 0; s < UA_WPT; s++) {
-            if (s < steps) dst[s] = em[s];
-        }
-        return;
-    }
-#endif
-#if UA_ABLATE == 3 /* fill+walk, skip scan/write-back */
-    asm volatile("" ::"v"(cnt), "v"(flags));
-    cnt = 0;
-    flags = 0;
-#endif
-
-    u32 excl, total;
-    d_block_scan<UA_TBLOCK>(tid, (u32)cnt, scan, excl, total);
-
-    if (MODE == MODE_COUNT) {
-        if (tid == 0) tile_cnt[t] = total;
-        return;
-    }
-    u64 *dst;
-    u32 lim = (u32)cnt;
-    if (MODE == MODE_STAGE) {
-        /* offs = the dense primary region's base, see enqueue_tiles */
-        dst = d_stage_dst(t, tid, (u32)cnt, excl, total, staging, stage_stride, offs,
-                          tile_cnt, lim);
-    } else { /* MODE_WRITE: (offs, partials) is the split flat scan */
-        dst = d.out +
-              (d_off(offs, partials, t) - d_off(offs, partials, d.tile_base)) + excl;
-    }
-    if (cnt > 0) {
-        if (A_ONLY) {
-            /* reconstruct emitted A-values from the per-chain masks */
-            constexpr int H = UA_WPT / 2;
-            u32 f = flags;
-            u32 k = 0;
-            while (f && k < lim) {
-                int s = __builtin_ctz(f);
-                f &= f - 1;
-                int idx = (s < H)
-                              ? w_i0 + __popc(amA & ((1u << s) - 1))
-                              : w_i0b + __popc(amB & ((1u << (s - H)) - 1));
-                dst[k++] = smem[aoff + idx];
-            }
-        } else {
-            u32 k = 0;
-#pragma unroll
-            for (int s = 0; s < UA_WPT; s++) {
-                if (flags & (1u << s)) {
-                    if (k < lim) dst[k] = em[s];
-                    k++;
-                }
-            }
+template <int OP, int MODE>
+__global__ __launch_bounds__(UA_TBLOCK) void k_tiles(
+    const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
+    const u32 *__restrict__ tile_a0, u64 total_tiles,
+    u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
+    const u64 *__restrict__ offs, const u64 *__restrict__ partials /* MODE_WRITE only */,
+    const u32 *__restrict__ isplit_in /* cached per-thread merge-path splits,
+        PACKED lo16 = i0 at diagonal s0, hi16 = i0b at smid (prepared batch:
+        inputs immutable, so splits are run-invariant like the tile
+        partition); null = compute */,
+    u32 *__restrict__ isplit_out /* store packed splits on the first run */,
+    const u32 *__restrict__ slab /* prepared batch's narrow records (then
+        tile_pair is its private copy with UA_NARROW_BIT), or null */) {
+    __shared__ __align__(16) u64 smem[UA_TILE_LDS];
+    __shared__ u32 scan[UA_TBLOCK / 64]; /* per-wave totals for d_block_scan */
+    u64 t = blockIdx.x;
+    /* all four tile words are requested together (one scalar round trip);
+     * the neighbour index is clamped, not branched on, so nothing past the
+     * arrays is read and no load waits on another's result */
+    u64 tn = (t + 1 < total_tiles) ? t + 1 : t;
+    u32 p = tile_pair[t];
+    u32 pn = tile_pair[tn];
+    u32 a0 = tile_a0[t];
+    u32 a0n = tile_a0[tn];
+    if constexpr ((OP == OP_INTERSECT || OP == OP_DIFF) && MODE == MODE_STAGE) {
+        /* eligibility rides in the first scalar round trip: nothing new
+         * stands between it and the fill */
+        const bool narrow = (slab != nullptr) && (p & UA_NARROW_BIT);
+        p &= ~UA_NARROW_BIT;
+        pn &= ~UA_NARROW_BIT;
+        if (narrow) {
+            tile_narrow<OP>(descs, p, pn, a0, a0n, t, tn, slab, smem, scan, staging,
+                            stage_stride, tile_cnt, offs, isplit_in, isplit_out);
+            return;
         }
     }
+    tile_wide<OP, MODE>(descs, p, pn, a0, a0n, t, tn, smem, scan, staging, stage_stride,
+                        tile_cnt, offs, partials, isplit_in, isplit_out);
 }
 
 /* ==================== kernel: bitonic chunk sort (segmented sort stage 1) ====================
@@ -1197,14 +1186,12 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact_small(
     u32 p = tile_pair[t];
     UaDesc d = descs[p];
     u64 goff = d_off(offs, partials, t) - d_off(offs, partials, tb[p]);
-    u64 cap = (op == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
-              : (op == OP_DIFF) ? d.n
-                                : (d.n + d.m);
+    u64 cap = d_pair_cap(d, op);
     if (goff >= cap) return;
     u64 room = cap - goff;
     if ((u64)cnt > room) cnt = (u32)room;
     u64 *dst = d.out + goff;
-    const u64 *src = prim ? prim + t * UA_STAGE_P : staging + t * stage_stride;
+    const u64 *src = d_stage_src(t, cnt, staging, stage_stride, prim);
     for (u32 i = 0; i < cnt; i++) dst[i] = src[i];
 }
 
@@ -1236,17 +1223,12 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact(
         if (cnt <= UA_COMPACT_SMALL) continue; /* k_compact_small's tiles */
         UaDesc d = descs[pair4[q]];
         u64 goff = off4[q] - d_off(offs, partials, tb[pair4[q]]);
-        /* pair out-capacity clamp (invalid duplicate/unsorted inputs must
-         * stay memory-safe, like the reference) */
-        u64 cap = (op == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
-                  : (op == OP_DIFF) ? d.n
-                                    : (d.n + d.m);
+        u64 cap = d_pair_cap(d, op);
         if (goff >= cap) continue;
         u64 room = cap - goff;
         if ((u64)cnt > room) cnt = (u32)room;
         u64 *dst = d.out + goff;
-        const u64 *src = (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
-                                                          : staging + t * stage_stride;
+        const u64 *src = d_stage_src(t, cnt, staging, stage_stride, prim);
         for (u32 i = lane; i < cnt; i += 64) dst[i] = src[i];
     }
 }
@@ -1341,9 +1323,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_tail_fused(
     /* per-pair capacity clamp, as k_compact: an element at pair offset g is
      * written iff g < cap (invalid duplicate/unsorted inputs stay
      * memory-safe) */
-    const u64 cap = (op == OP_INTERSECT) ? (d.n < d.m ? d.n : d.m)
-                    : (op == OP_DIFF)    ? d.n
-                                         : (d.n + d.m);
+    const u64 cap = d_pair_cap(d, op);
     if (tid == 0 && nx.pair != ck.pair) {
         /* pair's last chunk publishes the length, CLAMPED to cap; the old
          * k_pair_out publishes the unclamped sum.  They agree on valid
@@ -1371,9 +1351,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_tail_fused(
             }
             u32 cnt = s_ex[lo + 1] - s_ex[lo];
             u64 t = ck.t0 + lo;
-            /* mirrors the producer's primary-vs-overflow rule (k_tiles) */
-            const u64 *src = (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
-                                                              : staging + t * stage_stride;
+            const u64 *src = d_stage_src(t, cnt, staging, stage_stride, prim);
             dst[e] = src[e - s_ex[lo]];
         }
     } else {
@@ -1382,8 +1360,7 @@ __global__ __launch_bounds__(UA_BLOCK) void k_tail_fused(
             u32 cnt = s_ex[j + 1] - off;
             if (cnt == 0 || (u64)off >= room) continue;
             u64 t = ck.t0 + j;
-            const u64 *src = (prim && cnt <= (u32)UA_STAGE_P) ? prim + t * UA_STAGE_P
-                                                              : staging + t * stage_stride;
+            const u64 *src = d_stage_src(t, cnt, staging, stage_stride, prim);
             if ((u64)cnt > room - off) cnt = (u32)(room - off);
             u64 *o = dst + off;
             /* UA_TAIL_MLP independent loads in flight per lane, then the
