@@ -387,6 +387,11 @@ void orc_dec_seek_to_block(orc_dec *d, uint64_t uid, int whence) {
 /* codec.go:349 LinearSeek */
 void orc_dec_linear_seek(orc_dec *d, uint64_t seek) {
     for (;;) {
+        /* No next block: PeekNextBase answers MaxUint64, so for every seek
+         * below that the reference stops here too.  For seek == MaxUint64 the
+         * reference never stops (seek < v cannot hold); the oracle stops on
+         * the last block, which is where that uid would be. */
+        if (!d->pack || (size_t)d->block_idx + 1 >= d->pack->n_blocks) break;
         uint64_t v = orc_dec_peek_next_base(d);
         if (seek < v) break;
         d->block_idx++;

@@ -409,7 +409,12 @@ def test_packed_intersect_vs_oracle(eng, size, bs, m):
 
 
 def test_packed_32msb_splits(eng):
-    """Blocks forced by 32-MSB changes (codec.go:117) incl. huge bases."""
+    """Blocks forced by 32-MSB changes (codec.go:117) incl. huge bases.
+
+    This checks block splitting, not the byte format: the geometric inputs of
+    the packed tests in this file have one-byte deltas only (every control
+    byte is 0x00).  All 256 control bytes, the delta-length thresholds and the
+    1085-byte block are covered in tests/test_codec_tags_gpu.py."""
     rng = np.random.default_rng(SEED)
     big = [0xf000000000000000, 0xf00f000000000000, 0x00f00f0000000000,
            0x000f0f0000000000, 0x0f0f0f0f00000000]
