@@ -326,6 +326,78 @@ class Engine:
         dp.pack_totals = totals
         return dp
 
+    def decode_rows(self, dpb, afters=None, firsts=None, out_vals=None,
+                    out_row_offs=None, count_only=False):
+        """The UID matrix of a whole fan-out in ONE call (ua_rows_decode_dev):
+        handleUidPostings' per-key pl.Uids(opts) with opts.Intersect == nil
+        (worker/task.go:834-971, posting/list.go:1786-1902).  dpb is an
+        upload_pack_batch arena; row r is pack r's uids restricted to
+        x > afters[r] (0 keeps all), then cut by firsts[r] (> 0 the first
+        that many, < 0 the last, 0 all).  afters/firsts: None, one int for
+        every row, a sequence, or a CUDA tensor (int64 u64 bits / int32).
+        Returns (vals[:total], row_offs), the CSR form filter_rows and
+        union_rows take; with count_only vals is empty and row_offs holds
+        every key's List.Length (list.go:1345)."""
+        import torch
+        from dgraph_amd._lib import UaDRowPacks
+        dev = dpb.bases.device
+        n_rows = len(dpb.pbb) - 1
+        nb = int(dpb.pbb[n_rows])
+        if getattr(dpb, "_pbb_dev", None) is None:
+            dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
+
+        def per_row(x, np_dt, view_dt, t_dt):
+            if x is None:
+                return None
+            if isinstance(x, torch.Tensor):
+                if x.dtype != t_dt or x.numel() < n_rows:
+                    raise ValueError(f"per-row tensor needs {n_rows} x {t_dt}")
+                return x
+            a = np.asarray(x, dtype=np_dt)
+            a = np.full(n_rows, a, dtype=np_dt) if a.ndim == 0 else np.ascontiguousarray(a)
+            if a.size != n_rows:
+                raise ValueError(f"per-row argument needs {n_rows} entries, got {a.size}")
+            if n_rows == 0:
+                return None
+            return torch.from_numpy(a.view(view_dt)).to(dev)
+
+        t_after = per_row(afters, np.uint64, np.int64, torch.int64)
+        t_first = per_row(firsts, np.int32, np.int32, torch.int32)
+        if out_row_offs is None:
+            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        if out_row_offs.numel() < n_rows + 1:
+            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
+                             f"required {n_rows + 1}")
+        cap = 0
+        if not count_only:
+            full = int(sum(dpb.pack_totals))
+            if out_vals is None:
+                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
+            cap = out_vals.numel()
+            if t_after is None and t_first is None and cap < full:
+                raise ValueError(f"out_vals capacity {cap} < required {full}")
+        d = UaDRowPacks()
+        d.bases = dpb.bases.data_ptr()
+        d.num_uids = dpb.num_uids.data_ptr()
+        d.delta_offs = dpb.delta_offs.data_ptr()
+        d.deltas = dpb.deltas.data_ptr()
+        d.n_blocks = nb
+        d.row_block_base = dpb._pbb_dev.data_ptr()
+        d.n_rows = n_rows
+        d.after = t_after.data_ptr() if t_after is not None else None
+        d.first = t_first.data_ptr() if t_first is not None else None
+        d.out_vals = None if count_only else out_vals.data_ptr()
+        d.cap_vals = cap
+        d.out_row_offs = out_row_offs.data_ptr()
+        total = _u64()
+        rc = lib().ua_rows_decode_dev(self._ctx, C.byref(d), C.byref(total))
+        if rc == 3 and not count_only and total.value > cap:
+            raise ValueError(f"out_vals capacity {cap} < required {total.value}")
+        check(rc)
+        if count_only:
+            return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
+        return out_vals[:total.value], out_row_offs[:n_rows + 1]
+
     def intersect_packed_batch(self, dpb, vs, outs=None, afters=None):
         """Batched algo.IntersectCompressedWith: every pack of the fan-out in
         ONE grid.  vs: per-pack CUDA int64 tensors (may repeat one shared
@@ -660,6 +732,75 @@ def dest_uids(engine, rows):
     n = _u64()
     check(lib().ua_rows_union(engine._ctx, _hptr(vals), vals.size, _hptr(out), C.byref(n)))
     return out[:n.value]
+
+
+def _host_packs(packs):
+    """encode_flat tuples -> (ua_pack* array, keepalive)."""
+    from dgraph_amd._lib import UaBlock, UaPack
+    n = len(packs)
+    structs = (UaPack * max(n, 1))()
+    ptrs = (C.POINTER(UaPack) * max(n, 1))()
+    keep = []
+    for r, (bases, nums, offs, blob, _total) in enumerate(packs):
+        nb = len(bases)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        blocks = (UaBlock * max(nb, 1))()
+        for i in range(nb):
+            blocks[i].base = int(bases[i])
+            blocks[i].num_uids = int(nums[i])
+            blocks[i].deltas_len = int(offs[i + 1]) - int(offs[i])
+            blocks[i].deltas = C.cast(C.c_void_p(blob.ctypes.data + int(offs[i])),
+                                      C.POINTER(C.c_uint8))
+        structs[r].block_size = 0
+        structs[r].n_blocks = nb
+        structs[r].blocks = blocks
+        ptrs[r] = C.pointer(structs[r])
+        keep.append((blocks, blob))
+    return ptrs, (structs, keep)
+
+
+def _per_row(x, n, dtype):
+    a = np.asarray(x, dtype=dtype)
+    a = np.full(n, a, dtype=dtype) if a.ndim == 0 else np.ascontiguousarray(a)
+    if a.size != n:
+        raise ValueError(f"per-row argument needs {n} entries, got {a.size}")
+    return a if n else np.zeros(1, dtype=dtype)
+
+
+def _rows_decode_host(engine, packs, after, first, count_only):
+    n = len(packs)
+    ptrs, keep = _host_packs(packs)
+    a = _per_row(after, n, np.uint64)
+    f = _per_row(first, n, np.int32)
+    cap = 0 if count_only else sum(int(p[4]) for p in packs)
+    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
+    out_offs = np.empty(n + 1, dtype=np.uint64)
+    total = _u64()
+    check(lib().ua_rows_decode(engine._ctx, ptrs, n, _hptr(a),
+                               f.ctypes.data_as(C.POINTER(C.c_int32)),
+                               None if count_only else _hptr(out_vals), cap,
+                               _hptr(out_offs), C.byref(total)))
+    del keep
+    return out_vals, out_offs
+
+
+def uid_matrix(engine, packs, after=0, first=0):
+    """The UidMatrix of a handleUidPostings fan-out (worker/task.go:834-971)
+    on the opts.Intersect == nil branch as ONE call (ua_rows_decode): row r is
+    pl.Uids of pack r (posting/list.go:1786-1902), its uids > after (0 keeps
+    all), then the first `first` of them (or the last -first; 0 all).  packs:
+    tuples from encode_flat; after/first: one value or one per row.  Returns
+    a list of host uint64 arrays."""
+    out_vals, offs = _rows_decode_host(engine, packs, after, first, False)
+    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(len(packs))]
+
+
+def row_lengths(engine, packs, after=0):
+    """List.Length(readTs, afterUid) of every key (posting/list.go:1345-1363),
+    what count(uid) asks for: the count-only form of uid_matrix.  Returns a
+    host uint64 array of len(packs) lengths."""
+    _, offs = _rows_decode_host(engine, packs, after, 0, True)
+    return np.diff(offs)
 
 
 def update_dest_uids(engine, rows, dest):

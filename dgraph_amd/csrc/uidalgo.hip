@@ -1736,6 +1736,315 @@ __global__ __launch_bounds__(UA_BLOCK) void k_compact_pack(
     }
 }
 
+/* ==================== kernels: fan-out decode into a CSR UID matrix ====================
+ * ua_rows_decode_dev: count -> scan -> write, no staging
+ * area and no per-row host descriptor.  One wave per pb.UidBlock, UA_PKW
+ * blocks per workgroup as in k_packed; the decode body below is a second copy
+ * of k_packed's so that kernel keeps its code (the d_bitonic_sort_lds
+ * precedent, §4.6).  Every index that comes from device data (row boundaries,
+ * delta offsets, num_uids) is clamped before it is used: malformed input gives
+ * wrong answers, never an out-of-range access. */
+
+enum { RD_DROP = 0, RD_ALL = 1, RD_PART = 2 };
+
+struct UaRdBlk {
+    u64 base, off0;
+    u32 num, dlen;
+    bool ok; /* within the pack limits */
+};
+
+/* the 20 header bytes of block b; the delta range is clamped to the blob */
+__device__ __forceinline__ UaRdBlk d_rowdec_header(const u64 *__restrict__ bases,
+                                                   const u32 *__restrict__ nums,
+                                                   const u64 *__restrict__ doffs, u64 nb,
+                                                   u64 b) {
+    UaRdBlk h;
+    h.num = nums[b];
+    h.base = bases[b];
+    u64 blob = doffs[nb], o0 = doffs[b], o1 = doffs[b + 1];
+    if (o0 > blob) o0 = blob;
+    if (o1 < o0) o1 = o0;
+    if (o1 > blob) o1 = blob;
+    h.off0 = o0;
+    h.ok = h.num >= 1 && h.num <= UA_MAX_BLOCK_UIDS && o1 - o0 <= UA_MAX_DELTAS;
+    h.dlen = h.ok ? (u32)(o1 - o0) : 0;
+    return h;
+}
+
+/* the row of block b: the last r in [0, n_rows) with rbb[r] <= b (n_rows >= 1) */
+__device__ __forceinline__ u64 d_row_of(const u64 *__restrict__ rbb, u64 n_rows, u64 b) {
+    u64 lo = 0, hi = n_rows - 1;
+    while (lo < hi) {
+        u64 mid = (lo + hi + 1) >> 1;
+        if (rbb[mid] <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+/* row r's block range, clamped to [0, nb] and to rb0 <= rb1 */
+__device__ __forceinline__ void d_row_blocks(const u64 *__restrict__ rbb, u64 r, u64 nb,
+                                             u64 &rb0, u64 &rb1) {
+    rb0 = rbb[r];
+    rb1 = rbb[r + 1];
+    if (rb0 > nb) rb0 = nb;
+    if (rb1 > nb) rb1 = nb;
+    if (rb1 < rb0) rb1 = rb0;
+}
+
+/* List.Uids with Intersect == nil keeps x > after, and everything when after
+ * is 0 (codec.go:284, list.go:1797).  From the headers alone: a block whose
+ * base passes is kept whole, a block followed in its row by a base <= after
+ * is dropped whole, and the at most one other block per row is decoded. */
+__device__ __forceinline__ int d_rowdec_class(const u64 *__restrict__ bases, u64 b, u64 rb1,
+                                              u64 base, u64 after) {
+    if (after == 0 || base > after) return RD_ALL;
+    if (b + 1 < rb1 && bases[b + 1] <= after) return RD_DROP;
+    return RD_PART;
+}
+
+/* ListOptions.First over a row of L kept uids (list.go:1892-1900): the kept
+ * window [lo, hi) in row-rank space */
+__device__ __forceinline__ void d_row_window(u64 L, int32_t f, u64 &lo, u64 &hi) {
+    lo = 0;
+    hi = L;
+    if (f > 0) {
+        if ((u64)f < L) hi = (u64)f;
+    } else if (f < 0) {
+        u64 n = (u64)(-(int64_t)f); /* INT32_MIN negates in 64 bits */
+        if (n < L) lo = L - n;
+    }
+}
+
+/* k_packed's decode: deltas to LDS, lane-0 control-byte walk, per-lane
+ * 4-delta extract, wave prefix + base -> sdec[wv][0 .. num).  Called by every
+ * thread of the workgroup (three barriers inside); waves with active == false
+ * only pass the barriers. */
+__device__ __forceinline__ void d_rowdec_decode(bool active, int wv, int lane, const UaRdBlk &h,
+                                                const u8 *__restrict__ deltas,
+                                                u8 (*sdel)[UA_MAX_DELTAS],
+                                                u64 (*sdec)[UA_MAX_BLOCK_UIDS + 4],
+                                                u16 (*sgoff)[64]) {
+    if (active) {
+        for (u32 i = lane; i < h.dlen; i += 64) sdel[wv][i] = deltas[h.off0 + i];
+    }
+    __syncthreads(); /* sdel visible to lane 0's control-byte walk */
+
+    u32 ng = (h.num > 1) ? ((h.num + 2) >> 2) : 0; /* ceil((num-1)/4) <= 64 */
+    if (active && lane == 0) {
+        u32 o = 0; /* <= 17 * 63: the walk stays inside sdel whatever the bytes */
+        for (u32 g = 0; g < ng; g++) {
+            sgoff[wv][g] = (u16)o;
+            u8 tag = sdel[wv][o];
+            o += 5 + (tag & 3) + ((tag >> 2) & 3) + ((tag >> 4) & 3) + ((tag >> 6) & 3);
+        }
+    }
+    __syncthreads(); /* sgoff visible to all lanes */
+
+    u32 d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+    u64 s_local = 0;
+    if (active && lane < (int)ng) {
+        u32 o = sgoff[wv][lane];
+        u8 tag = sdel[wv][o];
+        const u8 *p = &sdel[wv][o + 1];
+        int l0 = (tag & 3) + 1, l1 = ((tag >> 2) & 3) + 1, l2 = ((tag >> 4) & 3) + 1,
+            l3 = ((tag >> 6) & 3) + 1;
+        d0 = d_load_le(p, l0);
+        p += l0;
+        d1 = d_load_le(p, l1);
+        p += l1;
+        d2 = d_load_le(p, l2);
+        p += l2;
+        d3 = d_load_le(p, l3);
+        s_local = (u64)d0 + d1 + d2 + d3;
+    }
+    u64 incl = s_local;
+    for (int o = 1; o < 64; o <<= 1) {
+        u64 x = __shfl_up(incl, o);
+        if (lane >= o) incl += x;
+    }
+    u64 excl = incl - s_local;
+    if (active && lane == 0) sdec[wv][0] = h.base;
+    if (active && lane < (int)ng) {
+        /* writes past num land in the +4 pad (codec.go:198) */
+        u64 acc = h.base + excl;
+        acc += d0; sdec[wv][lane * 4 + 1] = acc;
+        acc += d1; sdec[wv][lane * 4 + 2] = acc;
+        acc += d2; sdec[wv][lane * 4 + 3] = acc;
+        acc += d3; sdec[wv][lane * 4 + 4] = acc;
+    }
+    __syncthreads(); /* decoded block visible to every lane */
+}
+
+/* cnt[b] = how many uids of block b pass its row's after (launched when the
+ * call has an after array; k_rowdec_count_hdr otherwise) */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowdec_count(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, const u8 *__restrict__ deltas, u64 nb,
+    const u64 *__restrict__ rbb, u64 n_rows, const u64 *__restrict__ after,
+    u32 *__restrict__ cnt) {
+    __shared__ u8 sdel[UA_PKW][UA_MAX_DELTAS];
+    __shared__ u64 sdec[UA_PKW][UA_MAX_BLOCK_UIDS + 4];
+    __shared__ u16 sgoff[UA_PKW][64];
+
+    int wv = threadIdx.x >> 6;
+    int lane = threadIdx.x & 63;
+    u64 b = (u64)blockIdx.x * UA_PKW + wv;
+    /* no early return before the decode: its barriers need every thread */
+    bool inb = (b < nb);
+    UaRdBlk h = {};
+    int cls = RD_DROP;
+    u64 aft = 0;
+    if (inb) {
+        h = d_rowdec_header(bases, nums, doffs, nb, b);
+        if (h.ok) {
+            u64 r = d_row_of(rbb, n_rows, b), rb0, rb1;
+            d_row_blocks(rbb, r, nb, rb0, rb1);
+            aft = after[r];
+            cls = d_rowdec_class(bases, b, rb1, h.base, aft);
+        }
+    }
+    bool active = (cls == RD_PART);
+    d_rowdec_decode(active, wv, lane, h, deltas, sdel, sdec, sgoff);
+    if (!inb) return;
+    u32 c = (cls == RD_ALL) ? h.num : 0;
+    if (active) {
+        for (u32 s0 = 0; s0 < h.num; s0 += 64) {
+            u32 idx = s0 + lane;
+            bool ok = (idx < h.num) && (sdec[wv][idx] > aft);
+            c += (u32)__popcll(__ballot(ok));
+        }
+    }
+    if (lane == 0) cnt[b] = c;
+}
+
+/* k_rowdec_count without after: every block within the limits keeps all its
+ * uids, so the count is its header's num_uids — one thread per block */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowdec_count_hdr(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, u64 nb, u32 *__restrict__ cnt) {
+    u64 b = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (b >= nb) return;
+    UaRdBlk h = d_rowdec_header(bases, nums, doffs, nb, b);
+    cnt[b] = h.ok ? h.num : 0;
+}
+
+/* One thread per row boundary r in [0, n_rows].  Without first the block
+ * scan already is the CSR offsets: out_row_offs[r] = kept uids before row r's
+ * first block.  With first, kcnt[r] = the length of row r's kept window (and
+ * 0 at n_rows), to be scanned into the offsets by k_rowdec_offs. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowdec_rows(
+    const u64 *__restrict__ rbb, u64 n_rows, u64 nb, const u64 *__restrict__ offs,
+    const u64 *__restrict__ part, const int32_t *__restrict__ first /* or null */,
+    u32 *__restrict__ kcnt, u64 *__restrict__ out_row_offs) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    if (first == nullptr) {
+        u64 rb = rbb[r];
+        out_row_offs[r] = d_off(offs, part, rb < nb ? rb : nb);
+        return;
+    }
+    u32 k = 0;
+    if (r < n_rows) {
+        u64 rb0, rb1, lo, hi;
+        d_row_blocks(rbb, r, nb, rb0, rb1);
+        d_row_window(d_off(offs, part, rb1) - d_off(offs, part, rb0), first[r], lo, hi);
+        k = (u32)(hi - lo); /* <= sum(num_uids) < 2^32 */
+    }
+    kcnt[r] = k;
+}
+
+/* the window-length scan -> out_row_offs[0 .. n_rows] */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowdec_offs(const u64 *__restrict__ offs2,
+                                                          const u64 *__restrict__ part2,
+                                                          u64 n_rows,
+                                                          u64 *__restrict__ out_row_offs) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r <= n_rows) out_row_offs[r] = d_off(offs2, part2, r);
+}
+
+/* Decode block b and store the uids that pass after and fall into the row's
+ * first window straight to out_vals[out_row_offs[r] + rank - lo]: 64
+ * consecutive u64 per wave-step, each store bounded by cap_vals.  A block
+ * that kept nothing, or whose rank range misses the window, ends after its
+ * header. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowdec_write(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, const u8 *__restrict__ deltas, u64 nb,
+    const u64 *__restrict__ rbb, u64 n_rows, const u64 *__restrict__ after /* or null */,
+    const int32_t *__restrict__ first /* or null */, const u32 *__restrict__ cnt,
+    const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    const u64 *__restrict__ out_row_offs, u64 *__restrict__ out_vals, u64 cap_vals) {
+    __shared__ u8 sdel[UA_PKW][UA_MAX_DELTAS];
+    __shared__ u64 sdec[UA_PKW][UA_MAX_BLOCK_UIDS + 4];
+    __shared__ u16 sgoff[UA_PKW][64];
+
+    int wv = threadIdx.x >> 6;
+    int lane = threadIdx.x & 63;
+    u64 b = (u64)blockIdx.x * UA_PKW + wv;
+    /* no early return before the decode: its barriers need every thread */
+    UaRdBlk h = {};
+    u32 c = 0;
+    if (b < nb) {
+        h = d_rowdec_header(bases, nums, doffs, nb, b);
+        if (h.ok) c = cnt[b];
+    }
+    bool active = (c > 0);
+    bool all = true; /* every uid of the block passes after */
+    u64 aft = 0;
+    u64 pos0 = 0;         /* out_vals index of kept uid jlo of this block */
+    u32 jlo = 0, jhi = c; /* the block's kept uids [jlo, jhi) are stored */
+    if (active) {
+        u64 g = d_off(offs, part, b);
+        if (after == nullptr && first == nullptr) {
+            pos0 = g; /* the block scan is the output position */
+        } else {
+            u64 r = d_row_of(rbb, n_rows, b), rb0, rb1;
+            d_row_blocks(rbb, r, nb, rb0, rb1);
+            if (after != nullptr) {
+                aft = after[r];
+                all = (d_rowdec_class(bases, b, rb1, h.base, aft) == RD_ALL);
+            }
+            u64 g0 = d_off(offs, part, rb0);
+            u64 rank0 = g - g0; /* row rank of this block's first kept uid */
+            if (first == nullptr) {
+                pos0 = out_row_offs[r] + rank0;
+            } else {
+                u64 lo, hi;
+                d_row_window(d_off(offs, part, rb1) - g0, first[r], lo, hi);
+                u64 a = rank0 > lo ? rank0 : lo;
+                u64 e = rank0 + c < hi ? rank0 + c : hi;
+                if (a >= e) {
+                    active = false;
+                } else {
+                    jlo = (u32)(a - rank0);
+                    jhi = (u32)(e - rank0);
+                    pos0 = out_row_offs[r] + (a - lo);
+                }
+            }
+        }
+    }
+    d_rowdec_decode(active, wv, lane, h, deltas, sdel, sdec, sgoff);
+    if (!active) return;
+    u32 k = 0; /* kept uids of the block before this wave-step */
+    for (u32 s0 = 0; s0 < h.num && k < jhi; s0 += 64) {
+        u32 idx = s0 + lane;
+        bool ok = false;
+        u64 val = 0;
+        if (idx < h.num) {
+            val = sdec[wv][idx];
+            ok = all || val > aft;
+        }
+        u64 mask = __ballot(ok);
+        if (ok) {
+            u32 j = k + (u32)__popcll(mask & ((1ull << lane) - 1));
+            u64 p = pos0 + (j - jlo);
+            if (j >= jlo && j < jhi && p < cap_vals) out_vals[p] = val;
+        }
+        k += (u32)__popcll(mask);
+    }
+}
+
 /* ==================== kernels: GPU codec.Encode ====================
  * Parallel restatement of codec.go:57-136 (packBlock/Add): block boundaries
  * are 32-MSB changes (match32MSB :469) plus every block_size-th element
@@ -2111,7 +2420,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 13; }
+extern "C" int ua_version(void) { return 14; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -3750,6 +4059,128 @@ extern "C" int ua_decode_dev(ua_ctx *c, const ua_dpack *pk, uint64_t seek_uid, u
     return run_packed_locked(c, pk, seek_uid, nullptr, 0, out, out_n, 1);
 }
 
+/* ---- fan-out decode into a CSR UID matrix ----
+ * handleUidPostings' per-key pl.Uids(opts) loop with opts.Intersect == nil
+ * (worker/task.go:834-971, posting/list.go:1786-1902) as one call: count ->
+ * scan -> (window lengths -> scan ->) write, one sync, three u64 and the
+ * validation flag back to the host.  The argument checks come before c is
+ * touched. */
+#define UA_RD_MAX_BLOCKS (((u64)1 << 24) - 1) /* x 256 uids < 2^32: counts fit the u32 scan */
+
+extern "C" int ua_rows_decode_dev(ua_ctx *c, const ua_drowpacks *d, uint64_t *out_total) {
+    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
+    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals;
+    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
+        return UA_ERR_INVALID;
+    if (n_rows && !d->row_block_base) return UA_ERR_INVALID;
+    if (cap && !d->out_vals) return UA_ERR_INVALID;
+    if (n_rows == 0 && nb != 0) return UA_ERR_INVALID;
+    /* the row grids are u32 block counts */
+    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31)) return UA_ERR_INVALID;
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
+    const size_t rbb_bytes = d->row_block_base ? ro_bytes : 0;
+    /* the blob's length lives on the device: deltas is held to its first byte */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } ins[] = {{d->bases, nb * sizeof(u64)},
+               {d->num_uids, nb * sizeof(u32)},
+               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
+               {d->deltas, (size_t)(nb ? 1 : 0)},
+               {d->row_block_base, rbb_bytes},
+               {d->after, d->after ? n_rows * sizeof(u64) : 0},
+               {d->first, d->first ? n_rows * sizeof(int32_t) : 0}};
+    if (ranges_overlap(d->out_row_offs, ro_bytes, d->row_block_base, rbb_bytes) ||
+        ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
+        return UA_ERR_INVALID;
+    for (const auto &in : ins)
+        if (in.p && ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes))
+            return UA_ERR_INVALID;
+    const bool count_only = (d->out_vals == nullptr);
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (nb == 0) { /* every row is empty: nothing indexes an empty array */
+        HIP_TRY(hipMemsetAsync(d->out_row_offs, 0, ro_bytes, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->bytes_algo += 8 * (n_rows + 1);
+        *out_total = 0;
+        return UA_OK;
+    }
+    int rc;
+    const u64 nchunks2 = scan_chunks(n_rows + 1);
+    const size_t kcnt_bytes = align16((n_rows + 1) * sizeof(u32));
+    const size_t offs2_bytes = align16((n_rows + 1) * sizeof(u64));
+    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
+    if (d->first && (rc = ws_reserve(c, WS_KLEN, kcnt_bytes + offs2_bytes +
+                                                      (nchunks2 + 1) * sizeof(u64))))
+        return rc;
+    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    u32 *d_kcnt = nullptr;
+    u64 *d_offs2 = nullptr, *d_part2 = nullptr;
+    if (d->first) {
+        d_kcnt = (u32 *)c->ws[WS_KLEN];
+        d_offs2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes);
+        d_part2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes + offs2_bytes);
+    }
+    HIP_TRY(hipMemsetAsync(d_cnt + nb, 0, sizeof(u32), c->stream));
+    if ((rc = pack_validate_begin(c, d->num_uids, d->delta_offs, nb))) return rc;
+    u64 launches = 1;
+
+    const u32 nwg = (u32)((nb + UA_PKW - 1) / UA_PKW);
+    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    if (d->after)
+        hipLaunchKernelGGL(k_rowdec_count, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
+                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
+                           n_rows, d->after, d_cnt);
+    else
+        hipLaunchKernelGGL(k_rowdec_count_hdr, dim3((u32)((nb + UA_BLOCK - 1) / UA_BLOCK)),
+                           dim3(UA_BLOCK), 0, c->stream, d->bases, d->num_uids,
+                           d->delta_offs, nb, d_cnt);
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if ((rc = ws_scan(c, d_cnt, nb + 1, d_offs))) return rc;
+    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                       d->row_block_base, n_rows, nb, d_offs, d_part, d->first, d_kcnt,
+                       d->out_row_offs);
+    launches += 4;
+    if (d->first) {
+        enqueue_scan(d_kcnt, n_rows + 1, d_offs2, d_part2, nchunks2, c->stream);
+        hipLaunchKernelGGL(k_rowdec_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d_offs2,
+                           d_part2, n_rows, d->out_row_offs);
+        launches += 3;
+    }
+    if (!count_only) {
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        hipLaunchKernelGGL(k_rowdec_write, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
+                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
+                           n_rows, d->after, d->first, d_cnt, d_offs, d_part,
+                           d->out_row_offs, d->out_vals, cap);
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    }
+    /* out_row_offs[n_rows] is the published total; the blob length rides along
+     * for the byte count */
+    u64 total = 0, dbytes = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
+    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    if ((rc = pack_validate_end(c))) {
+        *out_total = 0;
+        return rc;
+    }
+    c->bytes_algo += dbytes + 20 * nb + 8 * (n_rows + 1) + 8 * total;
+    *out_total = total;
+    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+}
+
 /* ---- prepared pack fan-out (standing query plan) ---- */
 
 struct ua_pbatch {
@@ -4293,4 +4724,87 @@ extern "C" int ua_rows_union(ua_ctx *c, const uint64_t *vals, uint64_t total, ui
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out_n = len;
     return UA_OK;
+}
+
+/* host-pointer form of ua_rows_decode_dev: the UidMatrix of a per-key fan-out
+ * (worker/task.go:834-971, one pl.Uids(opts) per key with opts.Intersect ==
+ * nil) from host packs.  Flatten, upload, one device call, download; a null
+ * packs[r] is an empty row. */
+extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n_rows,
+                              const uint64_t *after, const int32_t *first,
+                              uint64_t *out_vals, uint64_t cap_vals, uint64_t *out_row_offs,
+                              uint64_t *out_total) {
+    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
+    if (n_rows && !packs) return UA_ERR_INVALID;
+    if (cap_vals && !out_vals) return UA_ERR_INVALID;
+    u64 nb = 0, db = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        if (!packs[r]) continue;
+        u64 pnb, pdb, ptu;
+        int prc = ua_pack_flat_sizes(packs[r], &pnb, &pdb, &ptu);
+        if (prc) return prc;
+        nb += pnb;
+        db += pdb;
+    }
+    if (nb > UA_RD_MAX_BLOCKS) return UA_ERR_INVALID;
+    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
+    std::vector<u32> nums(nb);
+    std::vector<u8> blob(db ? db : 1);
+    u64 b0 = 0, off0 = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        rbb[r] = b0;
+        if (!packs[r] || packs[r]->n_blocks == 0) continue;
+        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
+                                  doffs.data() + b0, blob.data() + off0);
+        if (prc) return prc;
+        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
+        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
+        b0 += pnb;
+        off0 += pdb;
+    }
+    rbb[n_rows] = nb;
+    doffs[nb] = off0;
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    size_t need = (nb + (nb + 1) + nro + n_rows) * 8 + (nb + n_rows) * 4 + blob.size();
+    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
+    u64 *d_bases = (u64 *)c->ws[WS_PACK];
+    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_after = d_rbb + nro;
+    u32 *d_nums = (u32 *)(d_after + n_rows);
+    int32_t *d_first = (int32_t *)(d_nums + nb);
+    u8 *d_blob = (u8 *)(d_first + n_rows);
+    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    if (after && n_rows)
+        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    if (first && n_rows)
+        HIP_TRY(hipMemcpyAsync(d_first, first, n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    /* the device call's sync covers the uploads: the host vectors live past it */
+    ua_drowpacks d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
+                      after ? d_after : nullptr, first ? d_first : nullptr,
+                      out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    u64 total = 0;
+    rc = ua_rows_decode_dev(c, &d, &total);
+    *out_total = total;
+    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
+    /* short capacity: the offsets are complete and still go back */
+    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
+    if (nv && rc == UA_OK)
+        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return rc;
 }

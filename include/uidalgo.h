@@ -293,6 +293,74 @@ int ua_rows_filter_dev(ua_ctx *, const ua_drows *, int mode, uint64_t *out_total
 int ua_rows_union_dev(ua_ctx *, const uint64_t *vals /* device */, uint64_t total,
                       uint64_t *out /* device, capacity total */, uint64_t *out_n);
 
+/* The UID matrix of a per-key fan-out, decoded in ONE call: packs in, CSR
+ * matrix out, one stream sync (since v14).  This is handleUidPostings
+ * (worker/task.go:834-971) on its ordinary branch, opts.Intersect == nil: one
+ * pl.Uids(opts) per key (posting/list.go:1786-1902), each result one row of
+ * UidMatrix.  The count-only form (out_vals NULL, cap_vals 0) gives every
+ * key's List.Length(readTs, afterUid) (posting/list.go:1345-1363), what
+ * count(uid) asks for.  The output is directly the input of
+ * ua_rows_filter_dev / ua_rows_union_dev.
+ *
+ * All rows' packs sit in one flat block arena, as in
+ * ua_intersect_packed_batch_dev; row r owns blocks
+ * [row_block_base[r], row_block_base[r+1]).  Unlike that call's boundaries,
+ * row_block_base is a DEVICE array: nothing per row crosses to the host.
+ *
+ * SEMANTICS ARE List.Uids', NOT ua_ptask.after_uid's AND NOT ua_decode_dev's
+ * seek.  Per row r, in this order:
+ *   1. the decoded uids of the row's blocks, in order, restricted to
+ *      x > after[r] — STRICTLY greater.  after[r] == 0 keeps everything, uid 0
+ *      included (codec.go:284, list.go:1797); UINT64_MAX gives an empty row.
+ *      (ua_decode_dev's seek keeps x >= seek.)
+ *   2. ListOptions.First (list.go:1892-1900) over what step 1 kept:
+ *      first[r] > 0 keeps the first first[r] of them, first[r] < 0 the last
+ *      -first[r], first[r] == 0 all.  INT32_MIN is legal (negated in 64 bits).
+ * after == NULL means all 0, first == NULL all 0.
+ *
+ * Capacity: *out_total is always the REQUIRED total and out_row_offs is always
+ * complete (out_row_offs[n_rows] == *out_total), whatever cap_vals is.  Every
+ * store into out_vals is bounded by cap_vals.  If *out_total > cap_vals and
+ * out_vals is not NULL the call returns UA_ERR_INVALID; out_vals is then
+ * unspecified but untouched past cap_vals: retry with the reported size, or
+ * size the buffer from a count-only call first.
+ *
+ * Rejected with UA_ERR_INVALID before the context is touched, nothing
+ * written: a null ctx, desc, out_total or out_row_offs; null pack arrays with
+ * n_blocks > 0; a null row_block_base with n_rows > 0; a null out_vals with
+ * cap_vals > 0; n_rows == 0 with n_blocks != 0; n_blocks > 2^24 - 1 (so the
+ * uids of one call number below 2^32 and every count fits the engine's u32
+ * scan); out_row_offs overlapping row_block_base; out_vals overlapping
+ * out_row_offs or any input (deltas is checked at its first byte: its length
+ * lives on the device).  n_rows == 0 and n_blocks == 0 are valid.
+ *
+ * Pack limits as everywhere: num_uids <= 256 and <= 1092 delta bytes per
+ * block, else UA_ERR_INVALID and *out_total = 0.
+ *
+ * Memory safety does not depend on the data: a row_block_base that is not
+ * non-decreasing from 0 to n_blocks, unsorted bases or garbage delta bytes
+ * give unspecified rows and offsets, never an out-of-range access (every
+ * index read from the device is clamped; delta_offs[n_blocks] is taken as the
+ * blob's length). */
+typedef struct {
+    /* flat block arena of all rows' packs */
+    const uint64_t *bases;          /* device [n_blocks] */
+    const uint32_t *num_uids;       /* device [n_blocks] */
+    const uint64_t *delta_offs;     /* device [n_blocks+1] */
+    const uint8_t *deltas;          /* device blob */
+    uint64_t n_blocks;
+    const uint64_t *row_block_base; /* DEVICE [n_rows+1], non-decreasing,
+                                     * [0] = 0, [n_rows] = n_blocks */
+    uint64_t n_rows;
+    const uint64_t *after;          /* device [n_rows] or NULL (= all 0) */
+    const int32_t *first;           /* device [n_rows] or NULL (= all 0) */
+    uint64_t *out_vals;             /* device, capacity cap_vals; NULL with
+                                     * cap_vals == 0 = count only */
+    uint64_t cap_vals;
+    uint64_t *out_row_offs;         /* device [n_rows+1] */
+} ua_drowpacks;
+int ua_rows_decode_dev(ua_ctx *, const ua_drowpacks *, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -369,6 +437,16 @@ int ua_rows_filter(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
  * buffer, so out may overlap vals in any way. */
 int ua_rows_union(ua_ctx *, const uint64_t *vals /* host */, uint64_t total,
                   uint64_t *out /* host, capacity total */, uint64_t *out_n);
+/* The handleUidPostings loop (worker/task.go:834-971) with opts.Intersect ==
+ * nil as ONE call: host form of ua_rows_decode_dev, same semantics (x >
+ * after[r], then first[r]), same capacity rule and checks.  packs[r] is row
+ * r's pack (NULL = an empty row); after and first are host arrays of n_rows
+ * or NULL; out_vals (host, capacity cap_vals; NULL with cap_vals == 0 = count
+ * only) and out_row_offs (host, n_rows+1) receive the CSR matrix.  On a
+ * short cap_vals the offsets and *out_total are still delivered. */
+int ua_rows_decode(ua_ctx *, const ua_pack *const *packs, uint64_t n_rows,
+                   const uint64_t *after, const int32_t *first, uint64_t *out_vals,
+                   uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_total);
 
 #ifdef __cplusplus
 }
