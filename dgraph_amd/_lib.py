@@ -147,6 +147,8 @@ def lib():
         L.ua_batch_destroy.restype = None
         if L.ua_version() >= 13:  # an older library via UA_LIB_PATH (A/B runs)
             L.ua_batch_info.argtypes = [C.c_void_p, C.c_void_p, _u64p, _u64p, _u64p]
+        if L.ua_version() >= 15:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_batch_fast_tiles.argtypes = [C.c_void_p, C.c_void_p, _u64p]
         L.ua_merge_batch_dev.argtypes = [C.c_void_p, C.POINTER(UaDPair), C.c_int, _u64p]
         L.ua_difference_batch_dev.argtypes = [C.c_void_p, C.POINTER(UaDPair), C.c_int, _u64p]
         L.ua_merge_all_batch_dev.argtypes = [C.c_void_p, C.POINTER(UaDPair), C.c_int, _u64p]

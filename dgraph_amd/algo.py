@@ -580,6 +580,13 @@ class Batch:
                                   C.byref(nb)))
         return {"tiles": t.value, "narrow_tiles": nt.value, "narrow_bytes": nb.value}
 
+    def fast_tiles(self):
+        """ua_batch_fast_tiles: how many narrow tiles take the sentinel walk
+        (0 before the first intersect/difference run, and without the cache)."""
+        n = _u64()
+        check(lib().ua_batch_fast_tiles(self._eng._ctx, self._h, C.byref(n)))
+        return n.value
+
     def close(self):
         if self._h:
             lib().ua_batch_destroy(self._eng._ctx, self._h)

@@ -392,6 +392,49 @@ __device__ __forceinline__ int tile_walk3x(const E *smembase, int aoff, int alen
     return cnt;
 }
 
+/* The same walk over a FAST narrow tile (see k_narrow): L is the tile's
+ * record in LDS, A at 0 and B at boff, each range closed by a sentinel, and
+ * the tile is full, so that every chain walks W / 2 steps and no step tests a
+ * range, clamps an index or masks itself off.  A step compares, sets its flag
+ * and mask bits, advances the taken side and reads that side's next element;
+ * the last step of a chain reads nothing.  flags, amA and amB are
+ * tile_walk3x's, bit for bit. */
+template <int OP, int W>
+__device__ __forceinline__ int tile_walk3x_fast(const u32 *L, int boff, int s0, int i0a,
+                                                int i0b, u32 &flags, u32 &amA, u32 &amB) {
+    static_assert(W <= 32 && W % 2 == 0, "masks are u32; two equal chains");
+    static_assert(OP == OP_INTERSECT || OP == OP_DIFF, "A-only ops");
+    constexpr int H = W / 2;
+    int ia = i0a, ja = boff + s0 - i0a; /* j counts from L, not from boff */
+    int ib = i0b, jb = boff + s0 + H - i0b;
+    u32 aA = L[ia], bA = L[ja];
+    u32 aB = L[ib], bB = L[jb];
+    u32 f = 0, mA = 0, mB = 0;
+    auto step = [&](int q, u32 &a, u32 &b, int &i, int &j, u32 &mask, int fshift)
+                    __attribute__((always_inline)) {
+        const bool t = a <= b;
+        const bool emit = (OP == OP_INTERSECT) ? (a == b) : (a < b);
+        f |= ((u32)emit) << (fshift + q);
+        mask |= ((u32)t) << q;
+        if (q + 1 < H) {
+            i += t ? 1 : 0;
+            j += t ? 0 : 1;
+            u32 r = L[t ? i : j];
+            a = t ? r : a;
+            b = t ? b : r;
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < H; q++) {
+        step(q, aA, bA, ia, ja, mA, 0);
+        step(q, aB, bB, ib, jb, mB, H);
+    }
+    flags = f;
+    amA = mA;
+    amB = mB;
+    return __popc(f);
+}
+
 /* MODE_STAGE: where a thread's emissions go (dst) and how many of them fit
  * (lim).  Clamped to the staging stride: invalid (duplicate/unsorted) inputs
  * can emit more than stride entries per tile; results there are unspecified,
@@ -540,13 +583,23 @@ __device__ __forceinline__ void d_write_a_only(const E *As, u32 flags, u32 amA, 
  * A prepared batch promises that its pairs' device contents do not change
  * while it lives.  On that promise it keeps, beside the tile partition and
  * the per-thread splits, a 32-bit tile-major copy of its inputs: one record
- * per tile, UA_NREC_W u32 at a fixed 16-byte-aligned stride,
+ * per tile, UA_NREC_W u32 at a fixed 16-byte-aligned stride.  A record holds
+ * a logical array L of alen + blen + 2 words, each range closed by a sentinel:
  *
- *   [0, alen)            low halves of the tile's A range
- *   [alen, alen + blen)  low halves of its B range
- *   [.., UA_TILE)        unused (anything; every index is clamped as ever)
- *   tail, 4 words:       the tile's common high half | low half of B's
- *                        lookahead d.v[b1] (0 when there is none) | 0 | 0
+ *   L[0, alen)                   low halves of the tile's A range
+ *   L[alen]                      sa = 0xFFFFFFFF
+ *   L[alen + 1, alen + 1 + blen) low halves of its B range
+ *   L[alen + 1 + blen]           sb = low half of B's lookahead d.v[b1] when
+ *                                there is one (has_bn), else 0xFFFFFFFF
+ *
+ * L[0, UA_TILE) are the record's first UA_TILE words (whatever L leaves of
+ * them is unused: anything), and its 4-word tail is
+ *
+ *   the tile's common high half | L[UA_TILE] | L[UA_TILE + 1] | fast
+ *
+ * with 0 where L is shorter.  In LDS the tile is L itself: A at aoff = 0, B at
+ * boff = alen + 1, so that sb is B's element blen, where the guarded walk has
+ * always looked for the lookahead.
  *
  * A tile is NARROW iff every element of its A range, of its B range and its
  * lookahead element share one value of x >> 32; k_narrow decides that from
@@ -555,30 +608,56 @@ __device__ __forceinline__ void d_write_a_only(const E *As, u32 flags, u32 amA, 
  * wide walk's flags, masks and splits bit for bit, on invalid inputs too.
  * Every other tile keeps the 64-bit fill and walk.  The record's address
  * depends on the tile index alone, its source needs no alignment work, and a
- * step reads 4 B per input element instead of 8. */
-#define UA_NREC_W (UA_TILE + 4) /* u32 per record: UA_TILE low halves + tail */
+ * step reads 4 B per input element instead of 8.
+ *
+ * A narrow tile is FAST (the tail's fast word is 1) iff also
+ *   (c0) alen + blen == UA_TILE: every thread walks UA_WPT steps;
+ *   (c1) no low half of its A or B range is 0xFFFFFFFF;
+ *   (c2) there is no lookahead, or every A element of the tile is <= it
+ *        (always so on sorted input).
+ * Such a tile takes tile_walk3x_fast, which tests no range: the sentinels end
+ * the ranges by value.  Its splits obey 0 <= i0 <= alen and
+ * 0 <= s - i0 <= blen (d_merge_path_tile), and i + j < UA_TILE at every step.
+ * So i == alen forces j < blen, where a = sa is above every b by c1: B is
+ * taken and nothing is emitted, as in the guarded walk.  And j == blen forces
+ * i < alen, where a <= sb by c2, or because sb is the maximum and, by c1, a is
+ * not: A is taken, and it emits on a == sb only where sb is the lookahead, as
+ * in the guarded walk.  No read therefore passes L[alen] on A's side or
+ * L[alen + 1 + blen] on B's, and flags and masks are the guarded walk's on
+ * every input.  (Memory safety does not rest on this: a chain advances three
+ * times from its split, which keeps any index inside the tile LDS.)  Partial
+ * tiles and tiles that miss c1 or c2 keep the guarded walk on the same
+ * record; the lookahead itself may be 0xFFFFFFFF. */
+#define UA_NREC_W (UA_TILE + 4) /* u32 per record: L[0, UA_TILE) + tail */
 #define UA_NARROW_BIT 0x80000000u /* in a batch-private tile-pair word; pair
                                    * indices are < 2^31 (n_pairs is an int) */
 #define UA_NROUNDS ((UA_TILE * 4) / (UA_TBLOCK * 16)) /* LDS-DMA rounds per record */
 static_assert((UA_TILE * 4) % (UA_TBLOCK * 16) == 0 && UA_NROUNDS >= 1,
               "a record's data is whole rounds of 16 B per lane");
 static_assert((UA_NREC_W * 4) % 16 == 0, "records stay 16-byte aligned");
-static_assert((UA_TILE + 1) * 4 <= UA_SMEMN * 8, "narrow tile + lookahead fit the tile LDS");
+static_assert((UA_TILE + 2 + UA_WPT / 2) * 4 <= UA_SMEMN * 8,
+              "narrow tile + both sentinels fit the tile LDS, and so does any "
+              "index the fast walk can form");
 
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 /* Builds the records and votes each tile's eligibility: one workgroup per
  * tile, list pointers at any 8-byte parity.  tile_pair_n[t] = tile_pair[t],
  * with UA_NARROW_BIT set on a narrow tile.  Every load of the tile is in
  * flight at once; thread 0, which holds the tile's first element and the
- * lookahead, publishes the reference high half through LDS.  A tile whose
- * partition words do not describe a sane range (possible only on unsorted
- * input) stays wide and is not copied. */
+ * lookahead, publishes the reference high half and the lookahead's low half
+ * through LDS and writes the two sentinels.  L[UA_TILE] and L[UA_TILE + 1]
+ * belong to the tail, which thread 0 stores: whoever holds one of them hands
+ * it over through LDS.  A tile whose partition words do not describe a sane
+ * range (possible only on unsorted input) stays wide and is not copied. */
 __global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
     const UaDesc *__restrict__ descs, const u32 *__restrict__ tile_pair,
     const u32 *__restrict__ tile_a0, u64 total_tiles, u32 *__restrict__ slab,
     u32 *__restrict__ tile_pair_n) {
-    __shared__ u32 sh_hi;
+    __shared__ u32 sh_hi, sh_look;
+    __shared__ u32 sh_tail[2]; /* L[UA_TILE], L[UA_TILE + 1] */
+    __shared__ u32 sh_bad;     /* the vote: the OR of every thread's bad bits */
     u64 t = blockIdx.x;
     int tid = threadIdx.x;
     u64 tn = (t + 1 < total_tiles) ? t + 1 : t;
@@ -594,8 +673,8 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
     bool sane = alen >= 0 && blen >= 0 && alen + blen >= 1 && alen + blen <= UA_TILE &&
                 (u64)a0 + (u64)alen <= d.n && (u64)b0 + (u64)blen <= d.m;
     u32 *rec = slab + t * UA_NREC_W;
-    u32 hi = 0, look_lo = 0;
-    int ok = sane ? 1 : 0;
+    u32 hi = 0;
+    int bad = sane ? 0 : 3; /* bit 0: not narrow; bit 1: misses c1 or c2 */
     if (sane) { /* workgroup-uniform */
         int tilelen = alen + blen;
         /* unconditional loads at clamped indices (a thread past the tile's
@@ -613,28 +692,51 @@ __global__ __launch_bounds__(UA_TBLOCK) void k_narrow(
         }
         u64 look = 0;
         if (tid == 0 && has_bn) look = d.v[b1];
-        if (tid == 0) sh_hi = (u32)(x[0] >> 32); /* element 0 exists: tilelen >= 1 */
+        if (tid == 0) {
+            sh_hi = (u32)(x[0] >> 32); /* element 0 exists: tilelen >= 1 */
+            sh_look = (u32)look;
+            sh_tail[0] = 0;
+            sh_tail[1] = 0;
+            sh_bad = 0;
+        }
         __syncthreads();
         hi = sh_hi;
+        const u32 look_lo = sh_look;
 #pragma unroll
         for (int k = 0; k < UA_WPT; k++) {
-            /* branch-free: a slot past the tile's end gets the clamped
-             * element's low half, which nothing reads */
-            ok &= ((u32)(x[k] >> 32) == hi);
-            rec[k * UA_TBLOCK + tid] = (u32)x[k];
+            /* branch-free: element e goes to L[e + (e >= alen)], past sa; a
+             * thread past the tile's end stores its clamped element again.
+             * Only element UA_TILE - 1 of a full tile can land on L[UA_TILE] */
+            int e = k * UA_TBLOCK + tid;
+            if (e > tilelen - 1) e = tilelen - 1;
+            u32 lo = (u32)x[k];
+            bad |= ((u32)(x[k] >> 32) != hi) ? 1 : 0;
+            bad |= (lo == 0xFFFFFFFFu || (has_bn && e < alen && lo > look_lo)) ? 2 : 0;
+            int dst = e + (e >= alen ? 1 : 0);
+            if (dst < UA_TILE) rec[dst] = lo;
+            else sh_tail[0] = lo;
         }
-        if (tid == 0 && has_bn) {
-            ok &= ((u32)(look >> 32) == hi);
-            look_lo = (u32)look;
+        if (tid == 0) {
+            if (has_bn) bad |= ((u32)(look >> 32) != hi) ? 1 : 0;
+            const u32 sb = has_bn ? look_lo : 0xFFFFFFFFu;
+            int isb = alen + 1 + blen; /* <= UA_TILE + 1 */
+            if (alen < UA_TILE) rec[alen] = 0xFFFFFFFFu;
+            else sh_tail[0] = 0xFFFFFFFFu;
+            if (isb < UA_TILE) rec[isb] = sb;
+            else sh_tail[isb - UA_TILE] = sb;
         }
+        if (bad) atomicOr(&sh_bad, (u32)bad); /* rare: most tiles vote nothing */
     }
-    ok = __syncthreads_and(ok);
+    __syncthreads();
+    if (sane) bad = (int)sh_bad;
     if (tid == 0) {
+        const bool narrow = !(bad & 1);
+        const bool fast = (bad == 0) && (alen + blen == UA_TILE);
         rec[UA_TILE + 0] = hi;
-        rec[UA_TILE + 1] = look_lo;
-        rec[UA_TILE + 2] = 0;
-        rec[UA_TILE + 3] = 0;
-        tile_pair_n[t] = p | (ok ? UA_NARROW_BIT : 0u);
+        rec[UA_TILE + 1] = sane ? sh_tail[0] : 0u;
+        rec[UA_TILE + 2] = sane ? sh_tail[1] : 0u;
+        rec[UA_TILE + 3] = fast ? 1u : 0u;
+        tile_pair_n[t] = p | (narrow ? UA_NARROW_BIT : 0u);
     }
 }
 
@@ -654,14 +756,15 @@ constexpr bool UA_DO_EMIT = (UA_ABLATE != 3);
  * segment and splits, the walk, the block scan and the write-back.  lds holds
  * the tile as E (u64, or u32 on a narrow tile): A at aoff, B at boff with its
  * lookahead as element blen when has_bn, and for union the two boundary
- * slots.  hi64 is a narrow tile's common high half (unused when E = u64). */
+ * slots.  hi64 is a narrow tile's common high half (unused when E = u64);
+ * fast (workgroup-uniform) sends a narrow tile through tile_walk3x_fast. */
 template <int OP, int MODE, typename E>
 __device__ __forceinline__ void tile_finish(
     const E *lds, int aoff, int alen, int boff, int blen, bool has_ab, bool has_bb,
     bool has_bn, u64 hi64, const UaDesc &d, u64 d0, u64 t, u32 *scan,
     u64 *__restrict__ staging, u64 stage_stride, u32 *__restrict__ tile_cnt,
     const u64 *__restrict__ offs, const u64 *__restrict__ partials, bool have_split,
-    u32 split_w, u32 *__restrict__ isplit_out) {
+    u32 split_w, u32 *__restrict__ isplit_out, bool fast) {
     /* intersect/difference emit A-values only: maskless walk, values rebuilt
      * from LDS at write-back; union/merge-all carry them in em[] */
     constexpr bool A_ONLY = (OP == OP_INTERSECT || OP == OP_DIFF);
@@ -679,8 +782,17 @@ __device__ __forceinline__ void tile_finish(
         sp = d_resolve_splits(lds, aoff, alen, boff, blen, sg, have_split, split_w,
                               isplit_out, t, tid);
         if constexpr (A_ONLY) {
-            cnt = tile_walk3x<OP, UA_WPT>(lds, aoff, alen, boff, blen, has_bn, sg.s0, sg.smid,
-                                          sg.s1, sp.i0, sp.i0b, flags, amA, amB);
+            bool walked = false;
+            if constexpr (sizeof(E) == 4) {
+                if (fast) { /* workgroup-uniform; a full tile: s0 = tid * UA_WPT */
+                    cnt = tile_walk3x_fast<OP, UA_WPT>(lds, boff, tid * UA_WPT, sp.i0, sp.i0b,
+                                                       flags, amA, amB);
+                    walked = true;
+                }
+            }
+            if (!walked)
+                cnt = tile_walk3x<OP, UA_WPT>(lds, aoff, alen, boff, blen, has_bn, sg.s0,
+                                              sg.smid, sg.s1, sp.i0, sp.i0b, flags, amA, amB);
         } else {
             u64 a_before = 0, b_before = 0;
             if constexpr (OP == OP_UNION) {
@@ -745,10 +857,11 @@ __device__ __forceinline__ void tile_finish(
 
 /* One narrow tile of k_tiles<OP_INTERSECT | OP_DIFF, MODE_STAGE>: the record
  * goes to LDS by LDS-DMA as soon as t is known (its address needs no
- * descriptor), descs[p] arrives behind it, and the walk runs on u32.  Indices,
- * clamps, masks, the cached split format, the scan and the staging are the
- * wide path's (tile_finish); emitted A-values get the tile's high half back on
- * the way to staging. */
+ * descriptor), descs[p] arrives behind it, and the walk runs on u32: the
+ * sentinel walk when the record's tail says the tile is fast, else the guarded
+ * one.  Masks, the cached split format, the scan and the staging are the wide
+ * path's (tile_finish); emitted A-values get the tile's high half back on the
+ * way to staging. */
 template <int OP>
 __device__ __forceinline__ void tile_narrow(
     const UaDesc *__restrict__ descs, u32 p, u32 pn, u32 a0, u32 a0n, u64 t, u64 tn,
@@ -764,7 +877,7 @@ __device__ __forceinline__ void tile_narrow(
     if (have_split) split_w = isplit_in[t * UA_TBLOCK + tid];
     u32 *s32 = (u32 *)smem;
     const u32 *rec = slab + t * UA_NREC_W;
-    u32x4 tl = {0, 0, 0, 0}; /* the record's tail: high half, lookahead, 0, 0 */
+    u32x4 tl = {0, 0, 0, 0}; /* the record's tail: high half, L[UA_TILE], L[UA_TILE + 1], fast */
     if constexpr (UA_DO_FILL) {
         int wv4 = tid >> 6, lane = tid & 63;
 #pragma unroll
@@ -783,18 +896,23 @@ __device__ __forceinline__ void tile_narrow(
     UaDesc d = descs[p];
     const UaTileGeom g = d_tile_geom(d, t, tn, p, pn, a0, a0n);
     constexpr int aoff = 0;
-    int boff = g.alen;
+    int boff = g.alen + 1; /* past sa */
+    bool fast;
     if constexpr (UA_DO_FILL) {
         /* the one drain (see the wide fill); all four tail words pass through
          * it, so no register of the load is reused, and waited for, earlier */
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(tl)::"memory");
-        if (tid == 0) s32[boff + g.blen] = tl.y; /* B's lookahead, element blen of B */
+        /* the two words of L behind the DMA part, in one 8-byte LDS store */
+        if (tid == 0) *(u32x2 *)(s32 + UA_TILE) = (u32x2){tl.y, tl.z};
+        fast = __builtin_amdgcn_readfirstlane(tl.w) != 0; /* uniform: a scalar branch */
+    } else {
+        fast = (g.alen + g.blen == UA_TILE); /* no record was read: walk what it would hold */
     }
     const u64 hi64 = (u64)tl.x << 32;
     __syncthreads();
     tile_finish<OP, MODE_STAGE>(s32, aoff, g.alen, boff, g.blen, false, false, g.has_bn, hi64,
                                 d, g.d0, t, scan, staging, stage_stride, tile_cnt, primary,
-                                nullptr, have_split, split_w, isplit_out);
+                                nullptr, have_split, split_w, isplit_out, fast);
 }
 
 /* One 64-bit tile of k_tiles: every op and mode, and every tile that is not
@@ -906,7 +1024,7 @@ __device__ __forceinline__ void tile_wide(
     __syncthreads();
     tile_finish<OP, MODE>(smem, aoff, alen, boff, blen, has_ab, has_bb, has_bn, 0, d, tg.d0, t,
                           scan, staging, stage_stride, tile_cnt, offs, partials, have_split,
-                          split_w, isplit_out);
+                          split_w, isplit_out, false);
 }
 
 template <int OP, int MODE>
@@ -2420,7 +2538,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 14; }
+extern "C" int ua_version(void) { return 15; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -3079,6 +3197,25 @@ extern "C" int ua_batch_info(ua_ctx *c, ua_batch *b, uint64_t *tiles, uint64_t *
     if (tiles) *tiles = b->view[0].T;
     if (narrow_tiles) *narrow_tiles = nn;
     if (narrow_bytes) *narrow_bytes = b->d_narrow ? b->narrow_bytes : 0;
+    return UA_OK;
+}
+
+/* How many tiles take the sentinel walk: the records' fast words, fetched on
+ * demand with one strided copy (a narrow tile's alone can be 1). */
+extern "C" int ua_batch_fast_tiles(ua_ctx *c, ua_batch *b, uint64_t *n) {
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!b || !n) return UA_ERR_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    u64 nf = 0;
+    if (b->view[0].slab) {
+        std::vector<u32> fw((size_t)b->view[0].T);
+        HIP_TRY(hipMemcpy2DAsync(fw.data(), sizeof(u32), b->view[0].slab + UA_TILE + 3,
+                                 UA_NREC_W * sizeof(u32), sizeof(u32), fw.size(),
+                                 hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (u32 w : fw) nf += (w != 0);
+    }
+    *n = nf;
     return UA_OK;
 }
 

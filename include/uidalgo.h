@@ -172,6 +172,13 @@ void ua_batch_destroy(ua_ctx *, ua_batch *);
  * and stay 0 when it is disabled or could not be allocated.  (since v13) */
 int ua_batch_info(ua_ctx *, ua_batch *, uint64_t *tiles, uint64_t *narrow_tiles,
                   uint64_t *narrow_bytes);
+/* How many of the narrow tiles take the sentinel-terminated walk: full tiles
+ * (2048 merge-path elements) none of whose low halves is 0xFFFFFFFF, each
+ * range of whose record is closed by a sentinel, so that the walk tests no
+ * range.  Every other narrow tile keeps the guarded walk; results do not
+ * depend on which one a tile takes.  Counted on demand from the records; 0
+ * until the 32-bit copy exists, and when it is disabled.  (since v15) */
+int ua_batch_fast_tiles(ua_ctx *, ua_batch *, uint64_t *n);
 /* batched pairwise algo.MergeSorted semantics (dedup union, uidlist.go:448) */
 int ua_merge_batch_dev(ua_ctx *, const ua_dpair *pairs, int n_pairs,
                        uint64_t *out_lens);
