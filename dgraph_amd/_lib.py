@@ -89,6 +89,25 @@ class UaDRowPacks(C.Structure):
     ]
 
 
+class UaDRowIsect(C.Structure):
+    _fields_ = [
+        ("bases", C.c_void_p),
+        ("num_uids", C.c_void_p),
+        ("delta_offs", C.c_void_p),
+        ("deltas", C.c_void_p),
+        ("n_blocks", _u64),
+        ("row_block_base", C.c_void_p),
+        ("n_rows", _u64),
+        ("after", C.c_void_p),
+        ("reserved", C.c_void_p),
+        ("shared", C.c_void_p),
+        ("m", _u64),
+        ("out_vals", C.c_void_p),
+        ("cap_vals", _u64),
+        ("out_row_offs", C.c_void_p),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -168,6 +187,12 @@ def lib():
             L.ua_rows_decode.argtypes = [C.c_void_p, C.POINTER(C.POINTER(UaPack)), _u64,
                                          _u64p, C.POINTER(C.c_int32), _u64p, _u64, _u64p,
                                          _u64p]
+        if L.ua_version() >= 16:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_rows_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDRowIsect),
+                                                       _u64p]
+            L.ua_rows_intersect_packed.argtypes = [
+                C.c_void_p, C.POINTER(C.POINTER(UaPack)), _u64, _u64p, _u64p, _u64, _u64p,
+                _u64, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

@@ -398,6 +398,73 @@ class Engine:
             return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
         return out_vals[:total.value], out_row_offs[:n_rows + 1]
 
+    def intersect_rows(self, dpb, shared, afters=None, out_vals=None, out_row_offs=None,
+                       count_only=False):
+        """The UID matrix of a whole fan-out under one filter list in ONE call
+        (ua_rows_intersect_packed_dev): handleUidPostings' per-key
+        pl.Uids(opts) with opts.Intersect != nil, i.e. one
+        algo.IntersectCompressedWith(pack, after, q.UidList) per key
+        (posting/list.go:1823-1829, uidlist.go:33).  dpb is an
+        upload_pack_batch arena; shared a CUDA int64 tensor of u64 bits,
+        sorted ascending and duplicate-free.  Row r is pack r's uids with
+        x >= afters[r] (INCLUSIVE, unlike decode_rows) and x in shared; there
+        is no first on this branch.  afters: None, one int for every row, a
+        sequence, or a CUDA int64 tensor.  Returns (vals[:total], row_offs),
+        the CSR form filter_rows and union_rows take; with count_only vals is
+        empty and row_offs holds every key's count under the filter."""
+        import torch
+        from dgraph_amd._lib import UaDRowIsect
+        dev = dpb.bases.device
+        n_rows = len(dpb.pbb) - 1
+        nb = int(dpb.pbb[n_rows])
+        m = shared.numel()
+        if shared.dtype != torch.int64:
+            raise ValueError("shared needs int64 (u64 bits)")
+        if getattr(dpb, "_pbb_dev", None) is None:
+            dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
+        t_after = None
+        if isinstance(afters, torch.Tensor):
+            if afters.dtype != torch.int64 or afters.numel() < n_rows:
+                raise ValueError(f"per-row tensor needs {n_rows} x {torch.int64}")
+            t_after = afters
+        elif afters is not None:
+            a = _per_row(afters, n_rows, np.uint64)
+            if n_rows:
+                t_after = torch.from_numpy(a.view(np.int64)).to(dev)
+        if out_row_offs is None:
+            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        if out_row_offs.numel() < n_rows + 1:
+            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
+                             f"required {n_rows + 1}")
+        cap = 0
+        if not count_only:
+            if out_vals is None:
+                full = int(sum(min(int(t), m) for t in dpb.pack_totals))
+                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
+            cap = out_vals.numel()
+        d = UaDRowIsect()
+        d.bases = dpb.bases.data_ptr()
+        d.num_uids = dpb.num_uids.data_ptr()
+        d.delta_offs = dpb.delta_offs.data_ptr()
+        d.deltas = dpb.deltas.data_ptr()
+        d.n_blocks = nb
+        d.row_block_base = dpb._pbb_dev.data_ptr()
+        d.n_rows = n_rows
+        d.after = t_after.data_ptr() if t_after is not None else None
+        d.shared = shared.data_ptr() if m else None
+        d.m = m
+        d.out_vals = None if count_only else out_vals.data_ptr()
+        d.cap_vals = cap
+        d.out_row_offs = out_row_offs.data_ptr()
+        total = _u64()
+        rc = lib().ua_rows_intersect_packed_dev(self._ctx, C.byref(d), C.byref(total))
+        if rc == 3 and not count_only and total.value > cap:
+            raise ValueError(f"out_vals capacity {cap} < required {total.value}")
+        check(rc)
+        if count_only:
+            return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
+        return out_vals[:total.value], out_row_offs[:n_rows + 1]
+
     def intersect_packed_batch(self, dpb, vs, outs=None, afters=None):
         """Batched algo.IntersectCompressedWith: every pack of the fan-out in
         ONE grid.  vs: per-pack CUDA int64 tensors (may repeat one shared
@@ -808,6 +875,30 @@ def row_lengths(engine, packs, after=0):
     host uint64 array of len(packs) lengths."""
     _, offs = _rows_decode_host(engine, packs, after, 0, True)
     return np.diff(offs)
+
+
+def uid_matrix_intersect(engine, packs, shared, after=0):
+    """The UidMatrix of a handleUidPostings fan-out on the opts.Intersect !=
+    nil branch as ONE call (ua_rows_intersect_packed): row r is
+    algo.IntersectCompressedWith(pack r, after, shared) (posting/list.go:
+    1823-1829, uidlist.go:33), the pack's uids with x >= after (inclusive)
+    that occur in shared; no first is applied on this branch.  packs: tuples
+    from encode_flat; shared: sorted duplicate-free host uint64 array; after:
+    one value or one per row.  Returns a list of host uint64 arrays."""
+    n = len(packs)
+    ptrs, keep = _host_packs(packs)
+    a = _per_row(after, n, np.uint64)
+    sh = np.ascontiguousarray(_np_u64(shared).ravel())
+    cap = sum(min(int(p[4]), sh.size) for p in packs)
+    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
+    offs = np.empty(n + 1, dtype=np.uint64)
+    total = _u64()
+    check(lib().ua_rows_intersect_packed(engine._ctx, ptrs, n, _hptr(a),
+                                         _hptr(sh), sh.size,
+                                         _hptr(out_vals), cap, _hptr(offs),
+                                         C.byref(total)))
+    del keep
+    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(n)]
 
 
 def update_dest_uids(engine, rows, dest):

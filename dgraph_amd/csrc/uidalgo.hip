@@ -2163,6 +2163,237 @@ __global__ __launch_bounds__(UA_BLOCK) void k_rowdec_write(
     }
 }
 
+/* ==================== kernel: fan-out intersect into a CSR UID matrix ====================
+ * ua_rows_intersect_packed_dev: every row's
+ * algo.IntersectCompressedWith(pack, after[r], shared) (uidlist.go:33), count
+ * -> scan -> write like the decode above and on its helpers.  One wave per
+ * block; the wave index goes through readfirstlane, so the header, the row
+ * lookup and the two bounding searches of `shared` are wave-uniform.
+ *
+ * A block is bounded from headers alone: its matches lie in shared[lo, hi)
+ * with lo = lower_bound(max(base, after[r])) and hi = lower_bound(the next
+ * base of the SAME row) (row r+1 may hold smaller uids than row r).  lo >= hi
+ * drops the block undecoded.  Otherwise the decoded last uid tightens hi
+ * (unless the range is within UA_RI_RATIO * num already: a shorter one would
+ * be too, with the same matches), and R = hi - lo against num_uids picks the
+ * match form:
+ *   list-driven  (R <= UA_RI_RATIO * num): 64 shared values per wave-step,
+ *                each looked up in the decoded block in LDS (k_packed's match);
+ *   block-driven (otherwise): 64 decoded uids per wave-step, at most 4 steps,
+ *                each >= key looked up in shared[lo, hi): about 256 * log2 m
+ *                probes per block however long the range is.
+ * Both emit in ascending order, and the choice depends only on values that the
+ * count and the write pass compute identically.  The count is clamped to num
+ * (only a shared list with duplicates could pass it) and the write pass stores
+ * match j only for j < cnt[b] and below cap_vals, so it stores what was
+ * counted whatever the data.
+ *
+ * A wave is latency-bound on its chain of dependent loads, so the wave-uniform
+ * searches probe 64 places per step (d_wave_lower_bound: 4 steps at m = 1M
+ * where a binary search takes 20), and lo and hi are searched in step.
+ * With UA_RI_KEEP the count pass also leaves, for a list-driven block of
+ * R <= 64, lo and the 64-bit match mask, and the write pass copies those
+ * shared values without decoding the block again.  Measured:
+ * profiles/rows_isect.md. */
+#ifndef UA_RI_RATIO
+#define UA_RI_RATIO 4 /* list-driven up to this many shared values per uid of
+                       * the block; 1, 4, 16 measured: profiles/rows_isect.md */
+#endif
+static_assert(UA_RI_RATIO >= 1 && UA_RI_RATIO <= 16, "UA_RI_RATIO is held to [1, 16]");
+#ifndef UA_RI_KEEP
+#define UA_RI_KEEP 1 /* 0 = the write pass always decodes and matches again */
+#endif
+#define UA_RI_NOKEEP UINT64_MAX /* keep[2b]: no mask was left for block b */
+
+/* N lower_bounds by the whole wave, in step so that their loads overlap:
+ * r[q] = lower_bound(a[q], n[q], key[q]).  64 probes per step cut a range to
+ * 1/64.  Every lane must be active; the results are the same in all of them.
+ * Every load is below n[q] whatever the data. */
+/* one search's step: its 64 probes narrow [lo, lo + len] (wave-uniform) */
+__device__ __forceinline__ void d_wave_narrow(u64 &lo, u64 &len, u64 step, bool in, u64 x,
+                                              u64 key) {
+    if (len == 0) return;
+    u64 mask = __ballot(!in || x >= key);
+    u64 f = mask ? (u64)__ffsll((long long)mask) - 1 : 64;
+    u64 end = lo + len;
+    lo += f * step; /* everything up to probe f - 1 is below key */
+    if (lo > end) lo = end;
+    len = (step - 1 < end - lo) ? step - 1 : end - lo;
+}
+
+template <int N> /* 1 or 2 */
+__device__ __forceinline__ void d_wave_lower_bound(const u64 *const (&a)[N], const u64 (&n)[N],
+                                                   const u64 (&key)[N], int lane, u64 (&r)[N]) {
+    u64 len[N]; /* the answer is in [r[q], r[q] + len[q]] */
+#pragma unroll
+    for (int q = 0; q < N; q++) {
+        r[q] = 0;
+        len[q] = n[q];
+    }
+    for (;;) {
+        u64 left = 0;
+#pragma unroll
+        for (int q = 0; q < N; q++) left |= len[q];
+        if (left == 0) break;
+        u64 step[N], x[N];
+        bool in[N];
+#pragma unroll
+        for (int q = 0; q < N; q++) { /* probes r + step - 1, r + 2 step - 1, ... */
+            step[q] = (len[q] + 63) >> 6;
+            u64 p = r[q] + (u64)(lane + 1) * step[q] - 1;
+            in[q] = (len[q] > 0) && (p < r[q] + len[q]);
+            x[q] = in[q] ? a[q][p] : UINT64_MAX;
+        }
+        d_wave_narrow(r[0], len[0], step[0], in[0], x[0], key[0]);
+        if (N > 1) d_wave_narrow(r[N > 1 ? 1 : 0], len[N > 1 ? 1 : 0], step[N > 1 ? 1 : 0],
+                                 in[N > 1 ? 1 : 0], x[N > 1 ? 1 : 0], key[N > 1 ? 1 : 0]);
+    }
+}
+
+__device__ __forceinline__ u64 d_wave_lower_bound(const u64 *a, u64 n, u64 key, int lane) {
+    const u64 *const as[1] = {a};
+    const u64 ns[1] = {n}, keys[1] = {key};
+    u64 r[1];
+    d_wave_lower_bound<1>(as, ns, keys, lane, r);
+    return r[0];
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(UA_BLOCK) void k_rowisect(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, const u8 *__restrict__ deltas, u64 nb,
+    const u64 *__restrict__ rbb, u64 n_rows, const u64 *__restrict__ after /* or null */,
+    const u64 *__restrict__ shared, u64 m, u32 *__restrict__ cnt /* WRITE: read */,
+    const u64 *__restrict__ offs, const u64 *__restrict__ part, u64 *__restrict__ out_vals,
+    u64 cap_vals, u64 *__restrict__ keep /* [2 * nb]: (lo, mask); WRITE: read; or null */) {
+    __shared__ u8 sdel[UA_PKW][UA_MAX_DELTAS];
+    __shared__ u64 sdec[UA_PKW][UA_MAX_BLOCK_UIDS + 4];
+    __shared__ u16 sgoff[UA_PKW][64];
+
+    int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int lane = threadIdx.x & 63;
+    u64 b = (u64)blockIdx.x * UA_PKW + wv;
+    /* no early return before the decode: its barriers need every thread */
+    bool inb = (b < nb);
+    UaRdBlk h = {};
+    u32 c = 0; /* WRITE: the count pass's matches of this block */
+    u64 key = 0, lo = 0, hi = 0;
+    u64 klo = UA_RI_NOKEEP, kmask = 0; /* the block's kept mask, if any */
+    bool active = false;
+    const u64 below = (1ull << lane) - 1;
+    if (inb) {
+        bool go = true;
+        if (WRITE) { /* a block that matched nothing ends here, before its header */
+            c = cnt[b];
+            go = (c > 0);
+            if (go && keep != nullptr) {
+                klo = keep[2 * b];
+                if (klo != UA_RI_NOKEEP) {
+                    kmask = keep[2 * b + 1];
+                    go = false;
+                }
+            }
+        }
+        if (go) {
+            h = d_rowdec_header(bases, nums, doffs, nb, b);
+            go = h.ok;
+        }
+        if (go) {
+            /* the next base rides with the header; it counts only inside the row */
+            u64 nbase = bases[b + 1 < nb ? b + 1 : b];
+            /* d_row_of by the whole wave: the last r with rbb[r] <= b */
+            u64 r = d_wave_lower_bound(rbb, n_rows, b + 1, lane), rb0, rb1;
+            r = r ? r - 1 : 0;
+            d_row_blocks(rbb, r, nb, rb0, rb1);
+            u64 aft = after ? after[r] : 0;
+            key = h.base > aft ? h.base : aft; /* x >= after[r]: Seek(afterUID, SeekStart) */
+            if (b + 1 < rb1) {
+                const u64 *const as[2] = {shared, shared};
+                const u64 ns[2] = {m, m}, keys[2] = {key, nbase};
+                u64 res[2];
+                d_wave_lower_bound<2>(as, ns, keys, lane, res);
+                lo = res[0];
+                hi = res[1];
+            } else {
+                lo = d_wave_lower_bound(shared, m, key, lane);
+                hi = m;
+            }
+            active = (lo < hi);
+        }
+    }
+    d_rowdec_decode(active, wv, lane, h, deltas, sdel, sdec, sgoff);
+    if (WRITE && klo != UA_RI_NOKEEP) { /* copy what the count pass marked */
+        u64 idx = klo + lane;
+        if (((kmask >> lane) & 1) && idx < m) {
+            u32 j = (u32)__popcll(kmask & below);
+            u64 p = d_off(offs, part, b) + j;
+            if (j < c && p < cap_vals) out_vals[p] = shared[idx];
+        }
+        return;
+    }
+    if (!active) {
+        if (!WRITE && inb && lane == 0) cnt[b] = 0;
+        return;
+    }
+    const u32 num = h.num;
+    u64 last = sdec[wv][num - 1];
+    /* tighten hi by the block's last uid, unless the range is list-driven
+     * already: a shorter range would be too, with the same matches */
+    if (hi - lo > (u64)UA_RI_RATIO * num && last != UINT64_MAX)
+        hi = lo + d_wave_lower_bound(shared + lo, hi - lo, last + 1, lane);
+    const u64 R = hi - lo;
+    const u64 pos0 = WRITE ? d_off(offs, part, b) : 0;
+    u32 k = 0; /* matches before this wave-step */
+    if (R <= (u64)UA_RI_RATIO * num) {
+        for (u64 s0 = lo; s0 < hi; s0 += 64) {
+            u64 idx = s0 + lane;
+            bool ok = false;
+            u64 val = 0;
+            if (idx < hi) {
+                val = shared[idx];
+                u64 pos = d_lower_bound(sdec[wv], num, val);
+                ok = (pos < num && sdec[wv][pos] == val);
+            }
+            u64 mask = __ballot(ok);
+            if (WRITE && ok) {
+                u32 j = k + (u32)__popcll(mask & below);
+                if (j < c && pos0 + j < cap_vals) out_vals[pos0 + j] = val;
+            }
+            k += (u32)__popcll(mask);
+            if (!WRITE && R <= 64) { /* the only step: its mask is the block's result */
+                klo = lo;
+                kmask = mask;
+            }
+        }
+    } else {
+        for (u32 s0 = 0; s0 < num; s0 += 64) {
+            u32 idx = s0 + lane;
+            bool ok = false;
+            u64 val = 0;
+            if (idx < num) {
+                val = sdec[wv][idx];
+                if (val >= key) {
+                    u64 pos = lo + d_lower_bound(shared + lo, R, val);
+                    ok = (pos < hi && shared[pos] == val);
+                }
+            }
+            u64 mask = __ballot(ok);
+            if (WRITE && ok) {
+                u32 j = k + (u32)__popcll(mask & below);
+                if (j < c && pos0 + j < cap_vals) out_vals[pos0 + j] = val;
+            }
+            k += (u32)__popcll(mask);
+        }
+    }
+    if (!WRITE && lane == 0) {
+        cnt[b] = k < num ? k : num;
+        if (keep != nullptr && k > 0) {
+            keep[2 * b] = klo;
+            keep[2 * b + 1] = kmask;
+        }
+    }
+}
+
 /* ==================== kernels: GPU codec.Encode ====================
  * Parallel restatement of codec.go:57-136 (packBlock/Add): block boundaries
  * are 32-MSB changes (match32MSB :469) plus every block_size-th element
@@ -2538,7 +2769,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 15; }
+extern "C" int ua_version(void) { return 16; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -4318,6 +4549,111 @@ extern "C" int ua_rows_decode_dev(ua_ctx *c, const ua_drowpacks *d, uint64_t *ou
     return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
 }
 
+/* ---- fan-out intersect into a CSR UID matrix ----
+ * handleUidPostings' per-key pl.Uids(opts) loop with opts.Intersect != nil
+ * (posting/list.go:1823-1829 -> algo.IntersectCompressedWith, uidlist.go:33)
+ * as one call: count -> scan -> write, one sync, two u64 and the validation
+ * flag back to the host.  There is no first, so the block scan is the output
+ * position and k_rowdec_rows publishes the offsets.  The argument checks come
+ * before c is touched. */
+extern "C" int ua_rows_intersect_packed_dev(ua_ctx *c, const ua_drowisect *d,
+                                            uint64_t *out_total) {
+    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
+    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals, m = d->m;
+    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
+        return UA_ERR_INVALID;
+    if (n_rows && !d->row_block_base) return UA_ERR_INVALID;
+    if (m && !d->shared) return UA_ERR_INVALID;
+    if (cap && !d->out_vals) return UA_ERR_INVALID;
+    if (d->reserved) return UA_ERR_INVALID; /* ua_drowpacks' first: none here */
+    if (n_rows == 0 && nb != 0) return UA_ERR_INVALID;
+    /* the row grids are u32 block counts; 8 * m is a byte count below */
+    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31) || m > (UINT64_MAX >> 3))
+        return UA_ERR_INVALID;
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
+    /* the blob's length lives on the device: deltas is held to its first byte */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } ins[] = {{d->bases, nb * sizeof(u64)},
+               {d->num_uids, nb * sizeof(u32)},
+               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
+               {d->deltas, (size_t)(nb ? 1 : 0)},
+               {d->row_block_base, d->row_block_base ? ro_bytes : 0},
+               {d->after, d->after ? n_rows * sizeof(u64) : 0},
+               {d->shared, m * sizeof(u64)}};
+    if (ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
+        return UA_ERR_INVALID;
+    for (const auto &in : ins)
+        if (in.p && (ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes) ||
+                     ranges_overlap(d->out_row_offs, ro_bytes, in.p, in.bytes)))
+            return UA_ERR_INVALID;
+    const bool count_only = (d->out_vals == nullptr);
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (nb == 0 || m == 0) { /* every row is empty: no launch, the packs are not read */
+        HIP_TRY(hipMemsetAsync(d->out_row_offs, 0, ro_bytes, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->bytes_algo += 8 * (n_rows + 1);
+        *out_total = 0;
+        return UA_OK;
+    }
+    int rc;
+    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
+    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    u64 *d_keep = nullptr; /* (lo, mask) per block, count pass -> write pass */
+    if (UA_RI_KEEP && !count_only) {
+        if ((rc = ws_reserve(c, WS_KLEN, nb * 2 * sizeof(u64)))) return rc;
+        d_keep = (u64 *)c->ws[WS_KLEN];
+    }
+    HIP_TRY(hipMemsetAsync(d_cnt + nb, 0, sizeof(u32), c->stream));
+    if ((rc = pack_validate_begin(c, d->num_uids, d->delta_offs, nb))) return rc;
+
+    const u32 nwg = (u32)((nb + UA_PKW - 1) / UA_PKW);
+    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_rowisect<false>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
+                       d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base, n_rows,
+                       d->after, d->shared, m, d_cnt, (const u64 *)nullptr,
+                       (const u64 *)nullptr, (u64 *)nullptr, (u64)0, d_keep);
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if ((rc = ws_scan(c, d_cnt, nb + 1, d_offs))) return rc;
+    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                       d->row_block_base, n_rows, nb, d_offs, d_part,
+                       (const int32_t *)nullptr, (u32 *)nullptr, d->out_row_offs);
+    if (!count_only) {
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        hipLaunchKernelGGL(k_rowisect<true>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
+                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
+                           n_rows, d->after, d->shared, m, d_cnt, (const u64 *)d_offs, d_part,
+                           d->out_vals, cap, d_keep);
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    }
+    u64 total = 0, dbytes = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    /* validation, count, scan (2), rows; then the write */
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], 5))) return rc;
+    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    if ((rc = pack_validate_end(c))) {
+        *out_total = 0;
+        return rc;
+    }
+    /* the call's input plus its output, not its traffic: a dropped block's
+     * deltas are never read, and a probed shared value is read more than once */
+    c->bytes_algo += dbytes + 20 * nb + 8 * (n_rows + 1) + 8 * m + 8 * total;
+    *out_total = total;
+    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+}
+
 /* ---- prepared pack fan-out (standing query plan) ---- */
 
 struct ua_pbatch {
@@ -4933,6 +5269,92 @@ extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n
                       out_vals ? d_ov : nullptr, cap_vals, d_oro};
     u64 total = 0;
     rc = ua_rows_decode_dev(c, &d, &total);
+    *out_total = total;
+    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
+    /* short capacity: the offsets are complete and still go back */
+    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
+    if (nv && rc == UA_OK)
+        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+/* host-pointer form of ua_rows_intersect_packed_dev: the UidMatrix of a
+ * per-key fan-out with opts.Intersect != nil (posting/list.go:1823-1829, one
+ * algo.IntersectCompressedWith per key, all against q.UidList) from host
+ * packs.  Flatten, upload, one device call, download; a null packs[r] is an
+ * empty row. */
+extern "C" int ua_rows_intersect_packed(ua_ctx *c, const ua_pack *const *packs,
+                                        uint64_t n_rows, const uint64_t *after,
+                                        const uint64_t *shared, uint64_t m,
+                                        uint64_t *out_vals, uint64_t cap_vals,
+                                        uint64_t *out_row_offs, uint64_t *out_total) {
+    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
+    if (n_rows && !packs) return UA_ERR_INVALID;
+    if (m && !shared) return UA_ERR_INVALID;
+    if (cap_vals && !out_vals) return UA_ERR_INVALID;
+    if (m > (UINT64_MAX >> 3)) return UA_ERR_INVALID;
+    u64 nb = 0, db = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        if (!packs[r]) continue;
+        u64 pnb, pdb, ptu;
+        int prc = ua_pack_flat_sizes(packs[r], &pnb, &pdb, &ptu);
+        if (prc) return prc;
+        nb += pnb;
+        db += pdb;
+    }
+    if (nb > UA_RD_MAX_BLOCKS) return UA_ERR_INVALID;
+    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
+    std::vector<u32> nums(nb);
+    std::vector<u8> blob(db ? db : 1);
+    u64 b0 = 0, off0 = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        rbb[r] = b0;
+        if (!packs[r] || packs[r]->n_blocks == 0) continue;
+        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
+                                  doffs.data() + b0, blob.data() + off0);
+        if (prc) return prc;
+        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
+        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
+        b0 += pnb;
+        off0 += pdb;
+    }
+    rbb[n_rows] = nb;
+    doffs[nb] = off0;
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    size_t need = (nb + (nb + 1) + nro + n_rows + m) * 8 + nb * 4 + blob.size();
+    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
+    u64 *d_bases = (u64 *)c->ws[WS_PACK];
+    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_after = d_rbb + nro;
+    u64 *d_shared = d_after + n_rows;
+    u32 *d_nums = (u32 *)(d_shared + m);
+    u8 *d_blob = (u8 *)(d_nums + nb);
+    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    if (after && n_rows)
+        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    if (m) HIP_TRY(hipMemcpyAsync(d_shared, shared, m * 8, hipMemcpyHostToDevice, c->stream));
+    /* the device call's sync covers the uploads: the host vectors live past it */
+    ua_drowisect d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
+                      after ? d_after : nullptr, nullptr, m ? d_shared : nullptr, m,
+                      out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    u64 total = 0;
+    rc = ua_rows_intersect_packed_dev(c, &d, &total);
     *out_total = total;
     if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
     /* short capacity: the offsets are complete and still go back */

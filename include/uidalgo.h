@@ -368,6 +368,81 @@ typedef struct {
 } ua_drowpacks;
 int ua_rows_decode_dev(ua_ctx *, const ua_drowpacks *, uint64_t *out_total);
 
+/* The UID matrix of a per-key fan-out under a filter list, in ONE call: packs
+ * and one shared sorted list in, CSR matrix out, one stream sync (since v16).
+ * This is handleUidPostings (worker/task.go:834-971) on its hot branch,
+ * opts.Intersect != nil: on an immutable pack pl.Uids(opts) is
+ * algo.IntersectCompressedWith(pack, opts.AfterUid, opts.Intersect)
+ * (posting/list.go:1823-1829, algo/uidlist.go:33), and every key of the
+ * fan-out gets the same q.UidList.  The count-only form (out_vals NULL,
+ * cap_vals 0) gives every key's count(uid) under the filter.  Input layout as
+ * ua_rows_decode_dev: one flat block arena, row r owns blocks
+ * [row_block_base[r], row_block_base[r+1]), row_block_base a DEVICE array.
+ * The output is directly the input of ua_rows_filter_dev / ua_rows_union_dev.
+ *
+ * SEMANTICS.  Row r is the decoded uids of the row's blocks, in order, with
+ *      x >= after[r]   and   x in shared.
+ *  - after is INCLUSIVE: IntersectCompressedWith does dec.Seek(afterUID,
+ *    SeekStart) (codec.go:279-329).  This is ua_ptask.after_uid's meaning and
+ *    is NOT ua_rows_decode_dev's x > after.  after[r] == 0 keeps everything;
+ *    after[r] == UINT64_MAX keeps UINT64_MAX if it is in both; after == NULL
+ *    means all 0.
+ *  - There is NO first.  On this branch getUidList returns
+ *    applyIntersectWith == false and Uids returns before list.go:1892: the
+ *    reference applies no ListOptions.First here.
+ *  - shared holds m uids, sorted ascending and duplicate-free; 0 and
+ *    UINT64_MAX are ordinary values.  m == 0 is valid: every row is empty.
+ *    If shared is not sorted and duplicate-free the rows are unspecified, but
+ *    every access stays in bounds and out_vals receives exactly what
+ *    out_row_offs counts.
+ *
+ * Capacity, count-only and the pack limits are exactly ua_rows_decode_dev's:
+ * *out_total is always the REQUIRED total and out_row_offs is always complete,
+ * whatever cap_vals is; every store into out_vals is bounded by cap_vals; if
+ * *out_total > cap_vals and out_vals is not NULL the call returns
+ * UA_ERR_INVALID with out_vals unspecified but untouched past cap_vals.  A
+ * block with num_uids > 256 or more than 1092 delta bytes gives
+ * UA_ERR_INVALID and *out_total = 0 (not looked for when n_blocks == 0 or
+ * m == 0: that call reads no pack).
+ *
+ * Rejected with UA_ERR_INVALID before the context is touched, nothing
+ * written: a null ctx, desc, out_total or out_row_offs; null pack arrays with
+ * n_blocks > 0; a null row_block_base with n_rows > 0; a null shared with
+ * m > 0; a null out_vals with cap_vals > 0; a non-null reserved; n_rows == 0
+ * with n_blocks != 0;
+ * n_blocks > 2^24 - 1; m >= 2^61; out_vals overlapping out_row_offs;
+ * out_vals or out_row_offs overlapping any input, shared and after included
+ * (deltas is checked at its first byte).
+ *
+ * Memory safety does not depend on the data, as for ua_rows_decode_dev.
+ *
+ * Stats: 6 launches (5 count-only); bytes_algorithmic grows by
+ * delta_offs[n_blocks] + 20*n_blocks + 8*(n_rows+1) + 8*m + 8*total, the size
+ * of the call's input plus its output, not its memory traffic (blocks dropped
+ * from their headers are never read; probed shared values are read again). */
+typedef struct {
+    /* flat block arena of all rows' packs */
+    const uint64_t *bases;          /* device [n_blocks] */
+    const uint32_t *num_uids;       /* device [n_blocks] */
+    const uint64_t *delta_offs;     /* device [n_blocks+1] */
+    const uint8_t *deltas;          /* device blob */
+    uint64_t n_blocks;
+    const uint64_t *row_block_base; /* DEVICE [n_rows+1], non-decreasing,
+                                     * [0] = 0, [n_rows] = n_blocks */
+    uint64_t n_rows;
+    const uint64_t *after;          /* device [n_rows] or NULL (= all 0) */
+    const void *reserved;           /* must be NULL: ua_drowpacks has first here
+                                     * (the two structs share their first nine
+                                     * slots), and this call has no first */
+    const uint64_t *shared;         /* device [m], sorted, duplicate-free */
+    uint64_t m;
+    uint64_t *out_vals;             /* device, capacity cap_vals; NULL with
+                                     * cap_vals == 0 = count only */
+    uint64_t cap_vals;
+    uint64_t *out_row_offs;         /* device [n_rows+1] */
+} ua_drowisect;
+int ua_rows_intersect_packed_dev(ua_ctx *, const ua_drowisect *, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -454,6 +529,19 @@ int ua_rows_union(ua_ctx *, const uint64_t *vals /* host */, uint64_t total,
 int ua_rows_decode(ua_ctx *, const ua_pack *const *packs, uint64_t n_rows,
                    const uint64_t *after, const int32_t *first, uint64_t *out_vals,
                    uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_total);
+/* The handleUidPostings loop with opts.Intersect != nil
+ * (posting/list.go:1823-1829: one IntersectCompressedWith per key against
+ * q.UidList) as ONE call: host form of ua_rows_intersect_packed_dev (since v16), same semantics
+ * (x >= after[r] and x in shared, no first), same capacity rule and checks.
+ * packs[r] is row r's pack (NULL = an empty row); after is a host array of
+ * n_rows or NULL; shared a host array of m sorted duplicate-free uids;
+ * out_vals (host, capacity cap_vals; NULL with cap_vals == 0 = count only) and
+ * out_row_offs (host, n_rows+1) receive the CSR matrix.  On a short cap_vals
+ * the offsets and *out_total are still delivered. */
+int ua_rows_intersect_packed(ua_ctx *, const ua_pack *const *packs, uint64_t n_rows,
+                             const uint64_t *after, const uint64_t *shared, uint64_t m,
+                             uint64_t *out_vals, uint64_t cap_vals,
+                             uint64_t *out_row_offs, uint64_t *out_total);
 
 #ifdef __cplusplus
 }
