@@ -108,6 +108,27 @@ class UaDRowIsect(C.Structure):
     ]
 
 
+class UaDRowMut(C.Structure):
+    _fields_ = [
+        ("bases", C.c_void_p),
+        ("num_uids", C.c_void_p),
+        ("delta_offs", C.c_void_p),
+        ("deltas", C.c_void_p),
+        ("n_blocks", _u64),
+        ("row_block_base", C.c_void_p),
+        ("n_rows", _u64),
+        ("after", C.c_void_p),
+        ("first", C.c_void_p),
+        ("mut_uids", C.c_void_p),
+        ("mut_ops", C.c_void_p),
+        ("row_mut_base", C.c_void_p),
+        ("n_mut", _u64),
+        ("out_vals", C.c_void_p),
+        ("cap_vals", _u64),
+        ("out_row_offs", C.c_void_p),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -193,6 +214,11 @@ def lib():
             L.ua_rows_intersect_packed.argtypes = [
                 C.c_void_p, C.POINTER(C.POINTER(UaPack)), _u64, _u64p, _u64p, _u64, _u64p,
                 _u64, _u64p, _u64p]
+        if L.ua_version() >= 17:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_rows_decode_mut_dev.argtypes = [C.c_void_p, C.POINTER(UaDRowMut), _u64p]
+            L.ua_rows_decode_mut.argtypes = [
+                C.c_void_p, C.POINTER(C.POINTER(UaPack)), _u64, _u64p, _u8p, _u64p, _u64p,
+                C.POINTER(C.c_int32), _u64p, _u64, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

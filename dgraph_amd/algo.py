@@ -398,6 +398,91 @@ class Engine:
             return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
         return out_vals[:total.value], out_row_offs[:n_rows + 1]
 
+    def decode_rows_mut(self, dpb, mut_uids, mut_ops, row_mut_base, afters=None,
+                        firsts=None, out_vals=None, out_row_offs=None, count_only=False):
+        """The UID matrix of a whole fan-out over LIVE lists in ONE call
+        (ua_rows_decode_mut_dev): handleUidPostings' per-key pl.Uids(opts) on
+        lists with a mutable layer, i.e. List.iterate's merge of the pack with
+        the picked postings (posting/list.go:1135-1251).  dpb is an
+        upload_pack_batch arena (an empty pack = a row without blocks); row r
+        owns mut_uids/mut_ops[row_mut_base[r]:row_mut_base[r+1]], strictly
+        ascending uids with op MUT_DEL deleting and any other op setting.
+        Row r = sorted((pack r - uids(M)) | sets(M)), then x > afters[r]
+        (0 keeps all), then firsts[r], as in decode_rows.  mut_uids (u64),
+        mut_ops (u8) and row_mut_base (u64, n_rows + 1) are host sequences or
+        CUDA tensors (int64 bits / uint8 / int64).  Returns (vals[:total],
+        row_offs); with count_only vals is empty and row_offs holds every
+        key's List.Length (list.go:1345).  The default capacity is
+        sum(pack_totals) + n_mut."""
+        import torch
+        from dgraph_amd._lib import UaDRowMut
+        dev = dpb.bases.device
+        n_rows = len(dpb.pbb) - 1
+        nb = int(dpb.pbb[n_rows])
+        if getattr(dpb, "_pbb_dev", None) is None:
+            dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
+
+        def dev_arr(x, n, np_dt, view_dt, t_dt, what):
+            if isinstance(x, torch.Tensor):
+                if x.dtype != t_dt or x.numel() < n:
+                    raise ValueError(f"{what} needs {n} x {t_dt}")
+                return x
+            a = np.ascontiguousarray(np.asarray(x, dtype=np_dt).ravel())
+            if a.size != n:
+                raise ValueError(f"{what} needs {n} entries, got {a.size}")
+            return torch.from_numpy(a.view(view_dt)).to(dev) if n else None
+
+        def per_row(x, np_dt, view_dt, t_dt):
+            if x is None:
+                return None
+            if not isinstance(x, torch.Tensor):
+                x = _per_row(x, n_rows, np_dt)[:n_rows]
+            return dev_arr(x, n_rows, np_dt, view_dt, t_dt, "per-row")
+
+        n_mut = mut_uids.numel() if isinstance(mut_uids, torch.Tensor) else len(mut_uids)
+        t_muids = dev_arr(mut_uids, n_mut, np.uint64, np.int64, torch.int64, "mut_uids")
+        t_mops = dev_arr(mut_ops, n_mut, np.uint8, np.uint8, torch.uint8, "mut_ops")
+        t_rmb = dev_arr(row_mut_base, n_rows + 1, np.uint64, np.int64, torch.int64,
+                        "row_mut_base") if n_mut else None
+        t_after = per_row(afters, np.uint64, np.int64, torch.int64)
+        t_first = per_row(firsts, np.int32, np.int32, torch.int32)
+        if out_row_offs is None:
+            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        if out_row_offs.numel() < n_rows + 1:
+            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
+                             f"required {n_rows + 1}")
+        cap = 0
+        if not count_only:
+            if out_vals is None:
+                full = int(sum(dpb.pack_totals)) + n_mut
+                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
+            cap = out_vals.numel()
+        d = UaDRowMut()
+        d.bases = dpb.bases.data_ptr()
+        d.num_uids = dpb.num_uids.data_ptr()
+        d.delta_offs = dpb.delta_offs.data_ptr()
+        d.deltas = dpb.deltas.data_ptr()
+        d.n_blocks = nb
+        d.row_block_base = dpb._pbb_dev.data_ptr()
+        d.n_rows = n_rows
+        d.after = t_after.data_ptr() if t_after is not None else None
+        d.first = t_first.data_ptr() if t_first is not None else None
+        d.mut_uids = t_muids.data_ptr() if n_mut else None
+        d.mut_ops = t_mops.data_ptr() if n_mut else None
+        d.row_mut_base = t_rmb.data_ptr() if n_mut else None
+        d.n_mut = n_mut
+        d.out_vals = None if count_only else out_vals.data_ptr()
+        d.cap_vals = cap
+        d.out_row_offs = out_row_offs.data_ptr()
+        total = _u64()
+        rc = lib().ua_rows_decode_mut_dev(self._ctx, C.byref(d), C.byref(total))
+        if rc == 3 and not count_only and total.value > cap:
+            raise ValueError(f"out_vals capacity {cap} < required {total.value}")
+        check(rc)
+        if count_only:
+            return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
+        return out_vals[:total.value], out_row_offs[:n_rows + 1]
+
     def intersect_rows(self, dpb, shared, afters=None, out_vals=None, out_row_offs=None,
                        count_only=False):
         """The UID matrix of a whole fan-out under one filter list in ONE call
@@ -874,6 +959,63 @@ def row_lengths(engine, packs, after=0):
     what count(uid) asks for: the count-only form of uid_matrix.  Returns a
     host uint64 array of len(packs) lengths."""
     _, offs = _rows_decode_host(engine, packs, after, 0, True)
+    return np.diff(offs)
+
+
+MUT_SET, MUT_DEL = 1, 2  # UA_MUT_SET / UA_MUT_DEL (posting/list.go:49-53)
+_EMPTY_PACK = (np.empty(0, np.uint64), np.empty(0, np.uint32), np.zeros(1, np.uint64),
+               np.empty(0, np.uint8), 0)
+
+
+def flatten_mutations(muts):
+    """Per-row lists of (uid, op) -> (mut_uids u64, mut_ops u8, row_mut_base
+    u64[n_rows + 1]), the flat form ua_rows_decode_mut takes."""
+    base = np.zeros(len(muts) + 1, dtype=np.uint64)
+    base[1:] = np.cumsum([len(m) for m in muts], dtype=np.uint64)
+    flat = [p for m in muts for p in m]
+    uids = np.array([int(u) for u, _ in flat], dtype=np.uint64)
+    ops = np.array([int(o) for _, o in flat], dtype=np.uint8)
+    return uids, ops, base
+
+
+def _rows_decode_mut_host(engine, packs, muts, after, first, count_only):
+    n = len(packs)
+    if len(muts) != n:
+        raise ValueError(f"muts needs {n} rows, got {len(muts)}")
+    packs = [_EMPTY_PACK if p is None else p for p in packs]
+    ptrs, keep = _host_packs(packs)
+    uids, ops, base = flatten_mutations(muts)
+    a = _per_row(after, n, np.uint64)
+    f = _per_row(first, n, np.int32)
+    cap = 0 if count_only else sum(int(p[4]) for p in packs) + uids.size
+    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
+    out_offs = np.empty(n + 1, dtype=np.uint64)
+    total = _u64()
+    check(lib().ua_rows_decode_mut(
+        engine._ctx, ptrs, n, _hptr(uids) if uids.size else None,
+        ops.ctypes.data_as(C.POINTER(C.c_uint8)) if uids.size else None, _hptr(base),
+        _hptr(a), f.ctypes.data_as(C.POINTER(C.c_int32)),
+        None if count_only else _hptr(out_vals), cap, _hptr(out_offs), C.byref(total)))
+    del keep
+    return out_vals, out_offs
+
+
+def uid_matrix_mut(engine, packs, muts, after=0, first=0):
+    """uid_matrix over LIVE lists (ua_rows_decode_mut): row r is pl.Uids of a
+    list with a mutable layer, List.iterate's merge (posting/list.go:1135-1251)
+    of pack r (a tuple from encode_flat, or None for a list without blocks)
+    with muts[r], a list of (uid, op) strictly ascending by uid: MUT_DEL
+    removes the uid, any other op sets it.  Then uids > after (0 keeps all),
+    then first, as in uid_matrix.  Returns a list of host uint64 arrays."""
+    out_vals, offs = _rows_decode_mut_host(engine, packs, muts, after, first, False)
+    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(len(packs))]
+
+
+def row_lengths_mut(engine, packs, muts, after=0):
+    """List.Length(readTs, afterUid) of every key on lists with a mutable
+    layer (posting/list.go:1345-1363): the count-only form of uid_matrix_mut.
+    Returns a host uint64 array of len(packs) lengths."""
+    _, offs = _rows_decode_mut_host(engine, packs, muts, after, 0, True)
     return np.diff(offs)
 
 

@@ -2394,6 +2394,442 @@ __global__ __launch_bounds__(UA_BLOCK) void k_rowisect(
     }
 }
 
+/* ==================== kernels: fan-out decode with mutation layers ====================
+ * ua_rows_decode_mut_dev: every row's List.Uids on a list
+ * with a mutable layer (List.iterate, posting/list.go:1135-1251), count -> scan
+ * -> k_rowdec_rows -> write like the two calls above and on their helpers.
+ *
+ * Output order is a sequence of nb + n_rows ITEMS: one head per row followed
+ * by that row's blocks, so row r's head is item min(rbb[r], nb) + r and block
+ * b of row r is item b + r + 1.  The head owns the row's mutations below the
+ * row's first base (all of them when the row has no block); block b owns
+ * those in [bases[b], bases[b+1]), the row's last block [bases[b], inf).  The
+ * item boundaries ribb[r] = min(rbb[r], nb) + r make the existing
+ * k_rowdec_rows / k_rowdec_offs produce the offsets and the first windows.
+ *
+ * The grids stay one thread or wave per BLOCK (k_rowmut_blocks, k_rowmut,
+ * k_rowmut_plain_write) and per ROW (k_rowmut_head, k_rowmut_head_write): an
+ * item is reached from its block or its row, never a block or row from an
+ * item index, so no inverse of the unvalidated rbb is needed.  pre[] is the
+ * exclusive scan of the per-mutation "emitted" flag (d_mut_emits); an item
+ * owning slice [s0, s1) emits pre[s1] - pre[s0] mutations.  A block with an
+ * empty slice keeps §4.7's header-only classes, decided by one thread per
+ * block; the wave passes run over the lists of the blocks that are left.
+ * Count and write share d_rowmut_locate, d_rowmut_slice, d_rowmut_keeps and
+ * d_mut_emits, and the write stores rank j only for j < cnt[item] and below
+ * cap_vals.
+ * Every index read from device data is clamped (d_row_blocks, d_row_muts) and
+ * every probe of mut_uids stays inside the row's clamped slice. */
+
+struct UaMutView {
+    const u64 *uids;  /* [n_mut] */
+    const u8 *ops;    /* [n_mut] */
+    const u64 *rmb;   /* row_mut_base [n_rows + 1] */
+    u64 n_mut;
+    const u64 *poffs; /* pre[]: split scan of the emitted flags, n_mut + 1 */
+    const u64 *ppart;
+};
+
+/* row r's mutation slice, clamped to [0, n_mut] and to m0 <= m1 */
+__device__ __forceinline__ void d_row_muts(const u64 *__restrict__ rmb, u64 r, u64 n_mut,
+                                           u64 &m0, u64 &m1) {
+    m0 = rmb[r];
+    m1 = rmb[r + 1];
+    if (m0 > n_mut) m0 = n_mut;
+    if (m1 > n_mut) m1 = n_mut;
+    if (m1 < m0) m1 = m0;
+}
+
+/* iterate emits a mutable posting iff mp.Op != Del (list.go:1217, 1229) and
+ * afterUid < mp.Uid (list.go:1146); after == 0 keeps all, as for the pack */
+__device__ __forceinline__ bool d_mut_emits(u8 op, u64 uid, u64 aft) {
+    return op != UA_MUT_DEL && (aft == 0 || uid > aft);
+}
+
+/* flag[j] = mutation j is emitted by its row, j in [0, n_mut); flag[n_mut] = 0 */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut_flags(UaMutView M, u64 n_rows,
+                                                           const u64 *__restrict__ after,
+                                                           u32 *__restrict__ flag) {
+    u64 j = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (j > M.n_mut) return;
+    u32 f = 0;
+    if (j < M.n_mut) {
+        u64 aft = after ? after[d_row_of(M.rmb, n_rows, j)] : 0;
+        f = d_mut_emits(M.ops[j], M.uids[j], aft);
+    }
+    flag[j] = f;
+}
+
+/* One thread per row boundary r in [0, n_rows]: the item boundary ribb[r],
+ * and for r < n_rows the head's count: the emitted mutations of the row's
+ * slice below the row's first base (all of them for a row without blocks). */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut_head(
+    const u64 *__restrict__ rbb, u64 n_rows, u64 nb, const u64 *__restrict__ bases,
+    UaMutView M, u32 *__restrict__ cnt, u64 *__restrict__ ribb) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    if (r == n_rows) {
+        ribb[r] = nb + n_rows; /* whatever rbb[n_rows] says: the items end here */
+        return;
+    }
+    u64 rb0, rb1, m0, m1;
+    d_row_blocks(rbb, r, nb, rb0, rb1);
+    ribb[r] = rb0 + r;
+    d_row_muts(M.rmb, r, M.n_mut, m0, m1);
+    u32 c = 0;
+    if (m0 < m1) {
+        u64 e = m1;
+        if (rb0 < rb1) e = m0 + d_lower_bound(M.uids + m0, m1 - m0, bases[rb0]);
+        c = (u32)(d_off(M.poffs, M.ppart, e) - d_off(M.poffs, M.ppart, m0));
+    }
+    cnt[rb0 + r] = c;
+}
+
+/* Per block, left by k_rowmut_blocks for the two wave passes: the block's row,
+ * with UA_MUT_OWNS set when the block owns mutations.  cnt[item] ==
+ * UA_MUT_WAVE asks the wave count pass for the block's count (every real
+ * count is smaller: 256 * n_blocks + n_mut <= 2^32 - 2). */
+#define UA_MUT_OWNS ((u64)1 << 63)
+#define UA_MUT_WAVE UINT32_MAX
+
+/* Block b's owned slice [s0, s1) of its row's clamped slice [m0, m1): the
+ * mutations in [base, the row's next base), or [base, inf) for the row's last
+ * block.  Every probe is inside [m0, m1). */
+__device__ __forceinline__ void d_rowmut_slice(const u64 *__restrict__ bases, u64 b, u64 rb1,
+                                               u64 base, const UaMutView &M, u64 m0, u64 m1,
+                                               u64 &s0, u64 &s1) {
+    s0 = s1 = m0;
+    if (m0 >= m1) return; /* a row with an empty layer skips both searches */
+    s0 = m0 + d_lower_bound(M.uids + m0, m1 - m0, base);
+    s1 = (b + 1 < rb1) ? m0 + d_lower_bound(M.uids + m0, m1 - m0, bases[b + 1]) : m1;
+    if (s1 < s0) s1 = s0; /* bases not ascending inside the row */
+}
+
+/* list[*n ...] = val for every lane with pred, one atomic per wave.  Every
+ * lane of the wave must call it. */
+__device__ __forceinline__ void d_wave_append(bool pred, u32 val, u32 *__restrict__ n,
+                                              u32 *__restrict__ list) {
+    const int lane = threadIdx.x & 63;
+    const u64 mask = __ballot(pred);
+    const int leader = mask ? __ffsll((long long)mask) - 1 : 0;
+    u32 base = 0;
+    if (mask && lane == leader) base = atomicAdd(n, (u32)__popcll(mask));
+    base = __shfl(base, leader);
+    if (pred) list[base + (u32)__popcll(mask & ((1ull << lane) - 1))] = val;
+}
+
+/* One thread per block: the block's row (brow), whether it owns mutations,
+ * and its count where the header decides it: a block without mutations that
+ * is kept or dropped whole (§4.7's classes), or a dropped block's mutations.
+ * Every other block is left to the wave count pass (UA_MUT_WAVE) and put on
+ * wlist; every owner is put on olist for the wave write pass.  The two wave
+ * passes run over these lists, so a sparse layer costs them next to nothing.
+ * The order of a list varies from run to run; no result depends on it. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut_blocks(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, u64 nb, const u64 *__restrict__ rbb, u64 n_rows,
+    const u64 *__restrict__ after /* or null */, UaMutView M, u32 *__restrict__ cnt,
+    u64 *__restrict__ brow, u32 *__restrict__ list_n /* [2], zeroed */,
+    u32 *__restrict__ wlist, u32 *__restrict__ olist) {
+    u64 b = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    bool owns = false, wave = false;
+    if (b < nb) {
+        UaRdBlk h = d_rowdec_header(bases, nums, doffs, nb, b);
+        u64 r = d_row_of(rbb, n_rows, b), rb0, rb1, m0, m1, s0, s1;
+        d_row_blocks(rbb, r, nb, rb0, rb1);
+        d_row_muts(M.rmb, r, M.n_mut, m0, m1);
+        if (!h.ok) m1 = m0;
+        d_rowmut_slice(bases, b, rb1, h.base, M, m0, m1, s0, s1);
+        int cls = h.ok ? d_rowdec_class(bases, b, rb1, h.base, after ? after[r] : 0) : RD_DROP;
+        owns = (s0 < s1);
+        brow[b] = r | (owns ? UA_MUT_OWNS : 0);
+        u32 c = UA_MUT_WAVE;
+        if (cls == RD_DROP) /* its mutations lie below the next base <= after: none emitted */
+            c = (u32)(d_off(M.poffs, M.ppart, s1) - d_off(M.poffs, M.ppart, s0));
+        else if (!owns && cls == RD_ALL)
+            c = h.num;
+        wave = (c == UA_MUT_WAVE);
+        cnt[b + r + 1] = c;
+    }
+    d_wave_append(wave, (u32)b, list_n + 0, wlist);
+    d_wave_append(owns, (u32)b, list_n + 1, olist);
+}
+
+/* What both wave passes know of block b, from brow: row, item, after, class
+ * and owned slice.  Wave-uniform. */
+struct UaMutBlk {
+    u64 r, item, aft, s0, s1;
+    int cls;
+};
+__device__ __forceinline__ UaMutBlk d_rowmut_locate(const u64 *__restrict__ bases, u64 nb,
+                                                    const u64 *__restrict__ rbb,
+                                                    const u64 *__restrict__ after,
+                                                    const UaMutView &M, u64 b, u64 base,
+                                                    u64 w) {
+    UaMutBlk k;
+    k.r = w & ~UA_MUT_OWNS;
+    k.item = b + k.r + 1;
+    k.aft = after ? after[k.r] : 0;
+    k.cls = RD_ALL;
+    k.s0 = k.s1 = 0;
+    if (after != nullptr || (w & UA_MUT_OWNS)) {
+        u64 rb0, rb1, m0, m1;
+        d_row_blocks(rbb, k.r, nb, rb0, rb1);
+        k.cls = d_rowdec_class(bases, b, rb1, base, k.aft);
+        if (w & UA_MUT_OWNS) {
+            d_row_muts(M.rmb, k.r, M.n_mut, m0, m1);
+            d_rowmut_slice(bases, b, rb1, base, M, m0, m1, k.s0, k.s1);
+        }
+    }
+    return k;
+}
+
+/* WRITE pass: where the item's ranks go.  The item's ranks [jlo, jhi) are
+ * stored from out_vals[pos0] on; false when its rank range misses its row's
+ * first window (k_rowdec_write's rule, in item space). */
+__device__ __forceinline__ bool d_rowmut_place(const UaMutBlk &k, u32 c, u64 n_items,
+                                               const int32_t *__restrict__ first,
+                                               const u64 *__restrict__ ribb,
+                                               const u64 *__restrict__ offs,
+                                               const u64 *__restrict__ part,
+                                               const u64 *__restrict__ out_row_offs,
+                                               u64 &pos0, u32 &jlo, u32 &jhi) {
+    jlo = 0;
+    jhi = c;
+    u64 g = d_off(offs, part, k.item);
+    if (first == nullptr) {
+        pos0 = g; /* no window: the item scan is the output position */
+        return true;
+    }
+    u64 ib0, ib1, lo, hi;
+    d_row_blocks(ribb, k.r, n_items, ib0, ib1);
+    u64 g0 = d_off(offs, part, ib0);
+    u64 rank0 = g - g0; /* row rank of this item's rank 0 */
+    d_row_window(d_off(offs, part, ib1) - g0, first[k.r], lo, hi);
+    u64 a = rank0 > lo ? rank0 : lo;
+    u64 e = rank0 + c < hi ? rank0 + c : hi;
+    if (a >= e) return false;
+    jlo = (u32)(a - rank0);
+    jhi = (u32)(e - rank0);
+    pos0 = out_row_offs[k.r] + (a - lo);
+    return true;
+}
+
+/* a uid of a block WITHOUT mutations is kept */
+__device__ __forceinline__ bool d_rowmut_keeps(const UaMutBlk &k, u64 val) {
+    return k.cls != RD_DROP && (k.aft == 0 || val > k.aft);
+}
+
+/* One wave per LISTED block, UA_PKW per workgroup-step.  WRITE == false, over
+ * wlist: the count of every block that k_rowmut_blocks left open: its kept
+ * uids plus its emitted mutations.  WRITE == true, over olist: an owner's
+ * kept uids and emitted mutations go to their merged ranks.  A kept uid i has
+ * rank keptpre[i] + (pre[lb_M(D[i])] - pre[s0]) in its item and emitted
+ * mutation j has (pre[j] - pre[s0]) + keptpre[lb_D(M[j])]; the first window
+ * applies in row-rank space as in k_rowdec_write. */
+template <bool WRITE>
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, const u8 *__restrict__ deltas, u64 nb,
+    const u64 *__restrict__ rbb, u64 n_rows, const u64 *__restrict__ after /* or null */,
+    const int32_t *__restrict__ first /* or null */, UaMutView M,
+    const u64 *__restrict__ brow, const u32 *__restrict__ list,
+    const u32 *__restrict__ list_n, const u64 *__restrict__ ribb,
+    u32 *__restrict__ cnt /* WRITE: read */, const u64 *__restrict__ offs,
+    const u64 *__restrict__ part, const u64 *__restrict__ out_row_offs,
+    u64 *__restrict__ out_vals, u64 cap_vals) {
+    __shared__ u8 sdel[UA_PKW][UA_MAX_DELTAS];
+    __shared__ u64 sdec[UA_PKW][UA_MAX_BLOCK_UIDS + 4];
+    __shared__ u16 sgoff[UA_PKW][64];
+    __shared__ u16 skp[UA_PKW][UA_MAX_BLOCK_UIDS + 2]; /* WRITE: kept uids before uid i */
+
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const u64 below = (1ull << lane) - 1;
+    u64 n_list = *list_n;
+    if (n_list > nb) n_list = nb;
+    /* every wave of the workgroup takes the same number of steps: the
+     * barriers inside need every thread.  A wave's LDS rows are its own. */
+    for (u64 i0 = (u64)blockIdx.x * UA_PKW; i0 < n_list; i0 += (u64)gridDim.x * UA_PKW) {
+        UaRdBlk h = {};
+        UaMutBlk k = {};
+        u32 c = 0;            /* WRITE: the count pass's count of this item */
+        u64 pos0 = 0;         /* WRITE: out_vals index of the item's rank jlo */
+        u32 jlo = 0, jhi = 0; /* WRITE: the item's ranks [jlo, jhi) are stored */
+        bool active = false;
+        u64 b = (i0 + wv < n_list) ? list[i0 + wv] : nb;
+        if (b < nb) {
+            const u64 w = brow[b];
+            c = cnt[b + (w & ~UA_MUT_OWNS) + 1];
+            active = WRITE ? (c > 0 && (w & UA_MUT_OWNS)) : (c == UA_MUT_WAVE);
+            if (active) { /* k_rowmut_blocks saw h.ok, or it had counted 0 */
+                h = d_rowdec_header(bases, nums, doffs, nb, b);
+                k = d_rowmut_locate(bases, nb, rbb, after, M, b, h.base, w);
+                active = h.ok;
+            }
+        }
+        if (WRITE && active)
+            active = d_rowmut_place(k, c, nb + n_rows, first, ribb, offs, part, out_row_offs,
+                                    pos0, jlo, jhi);
+        const bool mut = active && (k.s0 < k.s1);
+        const u64 nm = k.s1 - k.s0;
+        const u64 *ms = M.uids + k.s0;
+        const u64 pre0 = mut ? d_off(M.poffs, M.ppart, k.s0) : 0;
+        d_rowdec_decode(active, wv, lane, h, deltas, sdel, sdec, sgoff);
+
+        /* uid val of the block is kept; pos = lower_bound of val in the slice */
+        auto kept = [&](u64 val, u64 &pos) -> bool {
+            pos = 0;
+            if (!d_rowmut_keeps(k, val)) return false;
+            if (!mut) return true;
+            pos = d_lower_bound(ms, nm, val);
+            return !(pos < nm && ms[pos] == val);
+        };
+
+        if (!WRITE) {
+            if (!active) continue;
+            c = 0;
+            for (u32 s = 0; s < h.num; s += 64) {
+                u32 idx = s + lane;
+                u64 pos;
+                bool ok = (idx < h.num) && kept(sdec[wv][idx], pos);
+                c += (u32)__popcll(__ballot(ok));
+            }
+            if (mut) c += (u32)(d_off(M.poffs, M.ppart, k.s1) - pre0);
+            if (lane == 0) cnt[k.item] = c;
+            continue;
+        }
+
+        u32 kk = 0; /* kept uids of the block before this wave-step */
+        if (mut) {
+            for (u32 s = 0; s < h.num; s += 64) {
+                u32 idx = s + lane;
+                bool ok = false;
+                u64 val = 0, pos = 0;
+                if (idx < h.num) {
+                    val = sdec[wv][idx];
+                    ok = kept(val, pos);
+                }
+                u64 mask = __ballot(ok);
+                u32 j = kk + (u32)__popcll(mask & below);
+                if (idx < h.num) skp[wv][idx] = (u16)j;
+                if (ok) {
+                    j += (u32)(d_off(M.poffs, M.ppart, k.s0 + pos) - pre0);
+                    u64 p = pos0 + (j - jlo);
+                    if (j >= jlo && j < jhi && p < cap_vals) out_vals[p] = val;
+                }
+                kk += (u32)__popcll(mask);
+            }
+            if (lane == 0) skp[wv][h.num] = (u16)kk;
+        }
+        __syncthreads(); /* skp visible to every lane */
+        if (!mut) continue;
+        for (u64 s = 0; s < nm; s += 64) { /* the slice, 64 at a time however long */
+            u64 i = s + lane;
+            if (i >= nm) continue;
+            u64 uid = ms[i];
+            if (!d_mut_emits(M.ops[k.s0 + i], uid, k.aft)) continue;
+            u32 j = (u32)(d_off(M.poffs, M.ppart, k.s0 + i) - pre0) +
+                    skp[wv][d_lower_bound(sdec[wv], h.num, uid)];
+            u64 p = pos0 + (j - jlo);
+            if (j >= jlo && j < jhi && p < cap_vals) out_vals[p] = uid;
+        }
+    }
+}
+
+/* One wave per block: k_rowdec_write for the blocks that own no mutation,
+ * their positions taken from the item scan.  Owners are k_rowmut<true>'s. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut_plain_write(
+    const u64 *__restrict__ bases, const u32 *__restrict__ nums,
+    const u64 *__restrict__ doffs, const u8 *__restrict__ deltas, u64 nb,
+    const u64 *__restrict__ rbb, u64 n_rows, const u64 *__restrict__ after /* or null */,
+    const int32_t *__restrict__ first /* or null */, UaMutView M,
+    const u64 *__restrict__ brow, const u64 *__restrict__ ribb, const u32 *__restrict__ cnt,
+    const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    const u64 *__restrict__ out_row_offs, u64 *__restrict__ out_vals, u64 cap_vals) {
+    __shared__ u8 sdel[UA_PKW][UA_MAX_DELTAS];
+    __shared__ u64 sdec[UA_PKW][UA_MAX_BLOCK_UIDS + 4];
+    __shared__ u16 sgoff[UA_PKW][64];
+
+    int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int lane = threadIdx.x & 63;
+    u64 b = (u64)blockIdx.x * UA_PKW + wv;
+    /* no early return before the decode: its barriers need every thread */
+    UaRdBlk h = {};
+    UaMutBlk k = {};
+    u32 c = 0, jlo = 0, jhi = 0;
+    u64 pos0 = 0;
+    bool active = false;
+    if (b < nb) {
+        const u64 w = brow[b];
+        if (!(w & UA_MUT_OWNS)) c = cnt[b + w + 1];
+        if (c > 0) {
+            h = d_rowdec_header(bases, nums, doffs, nb, b);
+            k = d_rowmut_locate(bases, nb, rbb, after, M, b, h.base, w & ~UA_MUT_OWNS);
+            active = h.ok && d_rowmut_place(k, c, nb + n_rows, first, ribb, offs, part,
+                                            out_row_offs, pos0, jlo, jhi);
+        }
+    }
+    d_rowdec_decode(active, wv, lane, h, deltas, sdel, sdec, sgoff);
+    if (!active) return;
+    u32 kk = 0; /* kept uids of the block before this wave-step */
+    for (u32 s0 = 0; s0 < h.num && kk < jhi; s0 += 64) {
+        u32 idx = s0 + lane;
+        bool ok = false;
+        u64 val = 0;
+        if (idx < h.num) {
+            val = sdec[wv][idx];
+            ok = d_rowmut_keeps(k, val);
+        }
+        u64 mask = __ballot(ok);
+        if (ok) {
+            u32 j = kk + (u32)__popcll(mask & ((1ull << lane) - 1));
+            u64 p = pos0 + (j - jlo);
+            if (j >= jlo && j < jhi && p < cap_vals) out_vals[p] = val;
+        }
+        kk += (u32)__popcll(mask);
+    }
+}
+
+/* One wave per row: the head's emitted mutations go to out_vals.  The head
+ * is its row's first item, so its rank 0 is row rank 0; it ends at the first
+ * wave-step whose ranks lie past its count or its row's window. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowmut_head_write(
+    const u64 *__restrict__ rbb, u64 n_rows, u64 nb, const u64 *__restrict__ after,
+    const int32_t *__restrict__ first, UaMutView M, const u64 *__restrict__ ribb,
+    const u32 *__restrict__ cnt, const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    const u64 *__restrict__ out_row_offs, u64 *__restrict__ out_vals, u64 cap_vals) {
+    int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int lane = threadIdx.x & 63;
+    for (u64 r = (u64)blockIdx.x * UA_PKW + wv; r < n_rows; r += (u64)gridDim.x * UA_PKW) {
+        u64 rb0, rb1, m0, m1, lo = 0, hi;
+        d_row_blocks(rbb, r, nb, rb0, rb1);
+        u64 c = cnt[rb0 + r];
+        if (c == 0) continue;
+        hi = c;
+        if (first != nullptr) {
+            u64 ib0, ib1;
+            d_row_blocks(ribb, r, nb + n_rows, ib0, ib1);
+            d_row_window(d_off(offs, part, ib1) - d_off(offs, part, ib0), first[r], lo, hi);
+            if (hi > c) hi = c;
+        }
+        if (lo >= hi) continue;
+        d_row_muts(M.rmb, r, M.n_mut, m0, m1);
+        const u64 aft = after ? after[r] : 0;
+        const u64 pre0 = d_off(M.poffs, M.ppart, m0);
+        const u64 pos0 = out_row_offs[r]; /* the position of row rank lo */
+        for (u64 s = m0; s < m1; s += 64) {
+            if (d_off(M.poffs, M.ppart, s) - pre0 >= hi) break;
+            u64 i = s + lane;
+            if (i >= m1) continue;
+            u64 uid = M.uids[i];
+            if (!d_mut_emits(M.ops[i], uid, aft)) continue;
+            u64 j = d_off(M.poffs, M.ppart, i) - pre0, p = pos0 + (j - lo);
+            if (j >= lo && j < hi && p < cap_vals) out_vals[p] = uid;
+        }
+    }
+}
+
 /* ==================== kernels: GPU codec.Encode ====================
  * Parallel restatement of codec.go:57-136 (packBlock/Add): block boundaries
  * are 32-MSB changes (match32MSB :469) plus every block_size-th element
@@ -2736,7 +3172,7 @@ static thread_local hipError_t g_last_hip = hipSuccess;
 enum {
     WS_DESC = 0, WS_TB, WS_TPAIR, WS_TA0, WS_TCNT, WS_TOFF, WS_PARTIAL,
     WS_STAGE, WS_STAGEP, WS_POUT, WS_HU, WS_HV, WS_HOUT, WS_PACK, WS_SCRATCH_A,
-    WS_SCRATCH_B, WS_LOOK, WS_RPIV, WS_RKW, WS_KLEN, WS_COUNT
+    WS_SCRATCH_B, WS_LOOK, WS_RPIV, WS_RKW, WS_KLEN, WS_MUT, WS_COUNT
 };
 
 struct ua_ctx {
@@ -2769,7 +3205,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 16; }
+extern "C" int ua_version(void) { return 17; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -4654,6 +5090,183 @@ extern "C" int ua_rows_intersect_packed_dev(ua_ctx *c, const ua_drowisect *d,
     return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
 }
 
+/* ---- fan-out decode with mutation layers into a CSR UID matrix ----
+ * handleUidPostings' per-key pl.Uids(opts) loop on lists with a mutable layer
+ * (List.iterate, posting/list.go:1135-1251) as one call: flags -> scan ->
+ * counts -> scan -> rows (-> window lengths -> scan) -> write, one sync.
+ * n_mut == 0 IS ua_rows_decode_dev.  The argument checks come before c is
+ * touched.
+ *
+ * The bound on n_mut: every count goes through the u32 scan, and the largest
+ * is a row's window length (k_rowdec_rows' kcnt), at most the call's total
+ * 256 * n_blocks + n_mut.  That must stay below UA_MUT_WAVE = 2^32 - 1. */
+extern "C" int ua_rows_decode_mut_dev(ua_ctx *c, const ua_drowmut *d, uint64_t *out_total) {
+    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
+    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals, n_mut = d->n_mut;
+    if (n_mut == 0) { /* the same kernels, launches and stats as the plain call */
+        ua_drowpacks p = {d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
+                          d->row_block_base, n_rows, d->after, d->first,
+                          d->out_vals, cap, d->out_row_offs};
+        return ua_rows_decode_dev(c, &p, out_total);
+    }
+    if (!d->mut_uids || !d->mut_ops || !d->row_mut_base) return UA_ERR_INVALID;
+    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
+        return UA_ERR_INVALID;
+    if (n_rows == 0 || !d->row_block_base) return UA_ERR_INVALID;
+    if (cap && !d->out_vals) return UA_ERR_INVALID;
+    /* the row grids are u32 block counts */
+    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31)) return UA_ERR_INVALID;
+    if (n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
+    /* the blob's length lives on the device: deltas is held to its first byte */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } ins[] = {{d->bases, nb * sizeof(u64)},
+               {d->num_uids, nb * sizeof(u32)},
+               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
+               {d->deltas, (size_t)(nb ? 1 : 0)},
+               {d->after, d->after ? n_rows * sizeof(u64) : 0},
+               {d->first, d->first ? n_rows * sizeof(int32_t) : 0},
+               {d->mut_uids, n_mut * sizeof(u64)},
+               {d->mut_ops, n_mut}};
+    const void *const ro_ins[] = {d->row_block_base, d->mut_uids, d->mut_ops, d->row_mut_base};
+    const size_t ro_in_bytes[] = {ro_bytes, n_mut * sizeof(u64), n_mut, ro_bytes};
+    if (ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
+        return UA_ERR_INVALID;
+    for (int i = 0; i < 4; i++)
+        if (ranges_overlap(d->out_row_offs, ro_bytes, ro_ins[i], ro_in_bytes[i]) ||
+            ranges_overlap(d->out_vals, cap * sizeof(u64), ro_ins[i], ro_in_bytes[i]))
+            return UA_ERR_INVALID;
+    for (const auto &in : ins)
+        if (in.p && ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes))
+            return UA_ERR_INVALID;
+    const bool count_only = (d->out_vals == nullptr);
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const u64 n_items = nb + n_rows;
+    const u64 nchunks2 = scan_chunks(n_rows + 1), nchunksm = scan_chunks(n_mut + 1);
+    const size_t kcnt_bytes = align16((n_rows + 1) * sizeof(u32));
+    const size_t offs2_bytes = align16((n_rows + 1) * sizeof(u64));
+    const size_t flag_bytes = align16((n_mut + 1) * sizeof(u32));
+    const size_t poffs_bytes = align16((n_mut + 1) * sizeof(u64));
+    const size_t ppart_bytes = align16((nchunksm + 1) * sizeof(u64));
+    if ((rc = ws_reserve(c, WS_TCNT, (n_items + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (n_items + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_MUT, flag_bytes + poffs_bytes + ppart_bytes + align16(ro_bytes) +
+                                        nb * sizeof(u64) + (2 * nb + 4) * sizeof(u32))))
+        return rc;
+    if (d->first && (rc = ws_reserve(c, WS_KLEN, kcnt_bytes + offs2_bytes +
+                                                      (nchunks2 + 1) * sizeof(u64))))
+        return rc;
+    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    u32 *d_flag = (u32 *)c->ws[WS_MUT];
+    u64 *d_poffs = (u64 *)((u8 *)c->ws[WS_MUT] + flag_bytes);
+    u64 *d_ppart = (u64 *)((u8 *)d_poffs + poffs_bytes);
+    u64 *d_ribb = (u64 *)((u8 *)d_ppart + ppart_bytes);
+    u64 *d_brow = (u64 *)((u8 *)d_ribb + align16(ro_bytes)); /* [nb] */
+    u32 *d_listn = (u32 *)(d_brow + nb);                     /* [4]: two used */
+    u32 *d_wlist = d_listn + 4, *d_olist = d_wlist + nb;     /* [nb] each */
+    u32 *d_kcnt = nullptr;
+    u64 *d_offs2 = nullptr, *d_part2 = nullptr;
+    if (d->first) {
+        d_kcnt = (u32 *)c->ws[WS_KLEN];
+        d_offs2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes);
+        d_part2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes + offs2_bytes);
+    }
+    /* every item's count starts at 0: a malformed row_block_base leaves some unwritten */
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, (n_items + 1) * sizeof(u32), c->stream));
+    HIP_TRY(hipMemsetAsync(d_listn, 0, 4 * sizeof(u32), c->stream));
+    u64 launches = 0;
+    if (nb) {
+        if ((rc = pack_validate_begin(c, d->num_uids, d->delta_offs, nb))) return rc;
+        launches++;
+    }
+    const UaMutView M = {d->mut_uids, d->mut_ops, d->row_mut_base, n_mut, d_poffs, d_ppart};
+    const u32 nwg = (u32)((nb + UA_PKW - 1) / UA_PKW);
+    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+    const u32 hgrid = (u32)std::min<u64>((n_rows + UA_PKW - 1) / UA_PKW, (u64)1 << 20);
+    const u32 lgrid = std::min<u32>(nwg, 1u << 14); /* the listed blocks, in steps */
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_rowmut_flags, dim3((u32)(n_mut / UA_BLOCK + 1)), dim3(UA_BLOCK), 0,
+                       c->stream, M, n_rows, d->after, d_flag);
+    enqueue_scan(d_flag, n_mut + 1, d_poffs, d_ppart, nchunksm, c->stream);
+    hipLaunchKernelGGL(k_rowmut_head, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                       d->row_block_base, n_rows, nb, d->bases, M, d_cnt, d_ribb);
+    launches += 4;
+    if (nb) {
+        hipLaunchKernelGGL(k_rowmut_blocks, dim3((u32)((nb + UA_BLOCK - 1) / UA_BLOCK)),
+                           dim3(UA_BLOCK), 0, c->stream, d->bases, d->num_uids, d->delta_offs,
+                           nb, d->row_block_base, n_rows, d->after, M, d_cnt, d_brow, d_listn, d_wlist,
+                           d_olist);
+        hipLaunchKernelGGL(k_rowmut<false>, dim3(lgrid), dim3(UA_BLOCK), 0, c->stream, d->bases,
+                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
+                           n_rows, d->after, d->first, M, (const u64 *)d_brow,
+                           (const u32 *)d_wlist, (const u32 *)d_listn, (const u64 *)d_ribb,
+                           d_cnt, (const u64 *)nullptr, (const u64 *)nullptr,
+                           (const u64 *)nullptr, (u64 *)nullptr, (u64)0);
+        launches += 2;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if ((rc = ws_scan(c, d_cnt, n_items + 1, d_offs))) return rc;
+    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                       (const u64 *)d_ribb, n_rows, n_items, d_offs, d_part, d->first, d_kcnt,
+                       d->out_row_offs);
+    launches += 3;
+    if (d->first) {
+        enqueue_scan(d_kcnt, n_rows + 1, d_offs2, d_part2, nchunks2, c->stream);
+        hipLaunchKernelGGL(k_rowdec_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d_offs2,
+                           d_part2, n_rows, d->out_row_offs);
+        launches += 3;
+    }
+    if (!count_only) {
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        if (nb) {
+            hipLaunchKernelGGL(k_rowmut_plain_write, dim3(nwg), dim3(UA_BLOCK), 0, c->stream,
+                               d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
+                               d->row_block_base, n_rows, d->after, d->first, M,
+                               (const u64 *)d_brow, (const u64 *)d_ribb, (const u32 *)d_cnt,
+                               (const u64 *)d_offs, d_part, (const u64 *)d->out_row_offs,
+                               d->out_vals, cap);
+            hipLaunchKernelGGL(k_rowmut<true>, dim3(lgrid), dim3(UA_BLOCK), 0, c->stream,
+                               d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
+                               d->row_block_base, n_rows, d->after, d->first, M,
+                               (const u64 *)d_brow, (const u32 *)d_olist,
+                               (const u32 *)(d_listn + 1), (const u64 *)d_ribb, d_cnt,
+                               (const u64 *)d_offs, d_part, (const u64 *)d->out_row_offs,
+                               d->out_vals, cap);
+            launches += 2;
+        }
+        hipLaunchKernelGGL(k_rowmut_head_write, dim3(hgrid), dim3(UA_BLOCK), 0, c->stream,
+                           d->row_block_base, n_rows, nb, d->after, d->first, M,
+                           (const u64 *)d_ribb, (const u32 *)d_cnt, (const u64 *)d_offs, d_part,
+                           (const u64 *)d->out_row_offs, d->out_vals, cap);
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    }
+    u64 total = 0, dbytes = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    if (nb)
+        HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
+    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    if (nb && (rc = pack_validate_end(c))) {
+        *out_total = 0;
+        return rc;
+    }
+    /* the call's input plus its output, as for the plain call */
+    c->bytes_algo += dbytes + 20 * nb + 16 * (n_rows + 1) + 9 * n_mut + 8 * total;
+    *out_total = total;
+    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+}
+
 /* ---- prepared pack fan-out (standing query plan) ---- */
 
 struct ua_pbatch {
@@ -5269,6 +5882,104 @@ extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n
                       out_vals ? d_ov : nullptr, cap_vals, d_oro};
     u64 total = 0;
     rc = ua_rows_decode_dev(c, &d, &total);
+    *out_total = total;
+    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
+    /* short capacity: the offsets are complete and still go back */
+    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
+    if (nv && rc == UA_OK)
+        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+/* host-pointer form of ua_rows_decode_mut_dev: the UidMatrix of a per-key
+ * fan-out over lists with mutable layers (one pl.Uids(opts) per key through
+ * List.iterate, posting/list.go:1135-1251) from host packs and host mutation
+ * slices.  Flatten, upload, one device call, download; a null packs[r] is a
+ * row without blocks. */
+extern "C" int ua_rows_decode_mut(ua_ctx *c, const ua_pack *const *packs, uint64_t n_rows,
+                                  const uint64_t *mut_uids, const uint8_t *mut_ops,
+                                  const uint64_t *row_mut_base, const uint64_t *after,
+                                  const int32_t *first, uint64_t *out_vals, uint64_t cap_vals,
+                                  uint64_t *out_row_offs, uint64_t *out_total) {
+    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
+    if (n_rows && !packs) return UA_ERR_INVALID;
+    if (cap_vals && !out_vals) return UA_ERR_INVALID;
+    const u64 n_mut = (row_mut_base && n_rows) ? row_mut_base[n_rows] : 0;
+    if (n_mut == 0)
+        return ua_rows_decode(c, packs, n_rows, after, first, out_vals, cap_vals,
+                              out_row_offs, out_total);
+    if (!mut_uids || !mut_ops || n_mut > UINT32_MAX) return UA_ERR_INVALID;
+    u64 nb = 0, db = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        if (!packs[r]) continue;
+        u64 pnb, pdb, ptu;
+        int prc = ua_pack_flat_sizes(packs[r], &pnb, &pdb, &ptu);
+        if (prc) return prc;
+        nb += pnb;
+        db += pdb;
+    }
+    if (nb > UA_RD_MAX_BLOCKS || n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
+    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
+    std::vector<u32> nums(nb);
+    std::vector<u8> blob(db ? db : 1);
+    u64 b0 = 0, off0 = 0;
+    for (u64 r = 0; r < n_rows; r++) {
+        rbb[r] = b0;
+        if (!packs[r] || packs[r]->n_blocks == 0) continue;
+        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
+                                  doffs.data() + b0, blob.data() + off0);
+        if (prc) return prc;
+        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
+        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
+        b0 += pnb;
+        off0 += pdb;
+    }
+    rbb[n_rows] = nb;
+    doffs[nb] = off0;
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    /* u64 arrays first, then u32, then bytes: every array keeps its alignment */
+    size_t need = (nb + (nb + 1) + 2 * nro + n_rows + n_mut) * 8 + (nb + n_rows) * 4 +
+                  n_mut + blob.size();
+    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
+    u64 *d_bases = (u64 *)c->ws[WS_PACK];
+    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_rmb = d_rbb + nro;
+    u64 *d_after = d_rmb + nro, *d_muids = d_after + n_rows;
+    u32 *d_nums = (u32 *)(d_muids + n_mut);
+    int32_t *d_first = (int32_t *)(d_nums + nb);
+    u8 *d_mops = (u8 *)(d_first + n_rows);
+    u8 *d_blob = d_mops + n_mut;
+    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
+    if (nb) {
+        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_rmb, row_mut_base, nro * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_muids, mut_uids, n_mut * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_mops, mut_ops, n_mut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    if (after)
+        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
+    if (first)
+        HIP_TRY(hipMemcpyAsync(d_first, first, n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    /* the device call's sync covers the uploads: the host vectors live past it */
+    ua_drowmut d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
+                    after ? d_after : nullptr, first ? d_first : nullptr,
+                    d_muids, d_mops, d_rmb, n_mut,
+                    out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    u64 total = 0;
+    rc = ua_rows_decode_mut_dev(c, &d, &total);
     *out_total = total;
     if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
     /* short capacity: the offsets are complete and still go back */

@@ -443,6 +443,100 @@ typedef struct {
 } ua_drowisect;
 int ua_rows_intersect_packed_dev(ua_ctx *, const ua_drowisect *, uint64_t *out_total);
 
+/* The UID matrix of a per-key fan-out over LIVE lists, in ONE call: packs plus
+ * per-row mutation layers in, CSR matrix out, one stream sync (since v17).
+ * On a list with a mutable layer pl.Uids(opts) (List.Uids,
+ * posting/list.go:1786-1902) is not a decode but List.iterate
+ * (posting/list.go:1135-1251): a two-pointer merge of the pack with the picked
+ * mutable postings (pickPostings, list.go:1099-1133), in which a Del posting
+ * removes a uid and any other posting adds or overrides one.  The count-only
+ * form (out_vals NULL, cap_vals 0) gives every key's
+ * List.Length(readTs, afterUid) (list.go:1345-1363) on a mutated list.  Input
+ * layout as ua_rows_decode_dev (slots 0-8 are ua_drowpacks'), plus all rows'
+ * mutation slices concatenated: row r owns
+ * mut_uids/mut_ops[row_mut_base[r], row_mut_base[r+1]).  The output is directly
+ * the input of ua_rows_filter_dev / ua_rows_union_dev.
+ *
+ * SEMANTICS.  For row r let P be the decoded uids of the row's blocks, M the
+ * row's mutation slice and S the uids of M whose op is not UA_MUT_DEL.  Then
+ *   1. row = sorted((P - uids(M)) | S).  A set on a uid that P already holds
+ *      emits it once; a delete of an absent uid does nothing.  ANY op other
+ *      than UA_MUT_DEL sets (iterate tests only mp.Op != Del, list.go:1217, 1229,
+ *      so Ovr = 3 is a set).
+ *   2. then x > after[r], STRICTLY, on both sides of the merge: pitr.seek with
+ *      SeekCurrent for the pack and afterUid < mp.Uid for the layer
+ *      (list.go:1146).  after[r] == 0 keeps all.  This is ua_rows_decode_dev's
+ *      rule.
+ *   3. then ListOptions.First (list.go:1892-1900), word for word as in
+ *      ua_rows_decode_dev: first[r] > 0 keeps the first first[r] of them,
+ *      first[r] < 0 the last -first[r], first[r] == 0 all; INT32_MIN is legal.
+ *   4. after == NULL means all 0, first == NULL all 0.
+ * One divergence, not new: with a negative First the reference's own loop
+ * stops after the first collected uid (len(res) > opt.First, list.go:1868),
+ * so the window at 1892-1900 has nothing to cut; this call, like
+ * ua_rows_decode_dev, implements the window as lines 1892-1900 state it.
+ *
+ * What the caller hands over: each row's slice is pickPostings' result with
+ * only the newest version per uid kept (iterate's prevUid rule), strictly
+ * ascending by uid; a row under a delete-all marker (deleteBelowTs > 0,
+ * list.go:580-584) passes no blocks; only REF postings are in scope (a key
+ * whose layer holds value postings keeps the Go path).  The parity domain is
+ * uids >= 1 on both sides: iterate treats uid 0 as "iterator exhausted".  A 0
+ * in P behaves as in ua_rows_decode_dev.  A 0 in M, or a slice that is not
+ * strictly ascending, gives an unspecified row, but every access stays in
+ * bounds and out_vals receives nothing past what out_row_offs counts.
+ *
+ * Capacity, count-only and the pack limits are exactly ua_rows_decode_dev's:
+ * *out_total is always the REQUIRED total and out_row_offs is always complete,
+ * whatever cap_vals is; every store into out_vals is bounded by cap_vals; if
+ * *out_total > cap_vals and out_vals is not NULL the call returns
+ * UA_ERR_INVALID with out_vals unspecified but untouched past cap_vals.  A
+ * block with num_uids > 256 or more than 1092 delta bytes gives
+ * UA_ERR_INVALID and *out_total = 0.
+ *
+ * n_mut == 0 IS ua_rows_decode_dev: its checks, kernels, launches and stats
+ * (the three mutation arrays are then ignored and may be NULL).  Otherwise
+ * rejected with UA_ERR_INVALID before the context is touched, nothing written:
+ * everything ua_rows_decode_dev rejects; a null mut_uids, mut_ops or
+ * row_mut_base; n_rows == 0; 256 * n_blocks + n_mut > 2^32 - 2 (every count,
+ * the largest being one row's length, goes through the engine's u32 scan, and
+ * 2^32 - 1 marks a count that is still open);
+ * out_vals or out_row_offs overlapping mut_uids, mut_ops or row_mut_base.
+ *
+ * Memory safety does not depend on the data, as for ua_rows_decode_dev:
+ * row_mut_base entries are clamped to [0, n_mut] and to m0 <= m1, and every
+ * probe of mut_uids stays inside the row's clamped slice.
+ *
+ * Stats (n_mut > 0): 13 launches with blocks (10 count-only), 8 without (7
+ * count-only), 3 more with first; bytes_algorithmic grows by
+ * delta_offs[n_blocks] + 20*n_blocks + 16*(n_rows+1) + 9*n_mut + 8*total. */
+enum { UA_MUT_SET = 1, UA_MUT_DEL = 2 }; /* list.go:49-53 Set / Del */
+typedef struct {
+    /* slots 0-8: exactly ua_drowpacks' */
+    const uint64_t *bases;          /* device [n_blocks] */
+    const uint32_t *num_uids;       /* device [n_blocks] */
+    const uint64_t *delta_offs;     /* device [n_blocks+1] */
+    const uint8_t *deltas;          /* device blob */
+    uint64_t n_blocks;
+    const uint64_t *row_block_base; /* DEVICE [n_rows+1], non-decreasing,
+                                     * [0] = 0, [n_rows] = n_blocks */
+    uint64_t n_rows;
+    const uint64_t *after;          /* device [n_rows] or NULL (= all 0) */
+    const int32_t *first;           /* device [n_rows] or NULL (= all 0) */
+    const uint64_t *mut_uids;       /* device [n_mut]: all rows' picked postings,
+                                     * concatenated; strictly ascending inside a row */
+    const uint8_t *mut_ops;         /* device [n_mut]: UA_MUT_DEL deletes; ANY other
+                                     * value sets */
+    const uint64_t *row_mut_base;   /* DEVICE [n_rows+1], non-decreasing, [0] = 0,
+                                     * [n_rows] = n_mut; NULL with n_mut == 0 */
+    uint64_t n_mut;
+    uint64_t *out_vals;             /* device, capacity cap_vals; NULL with
+                                     * cap_vals == 0 = count only */
+    uint64_t cap_vals;
+    uint64_t *out_row_offs;         /* device [n_rows+1] */
+} ua_drowmut;                       /* 16 slots, 128 bytes: n_mut at 96, cap_vals at 112 */
+int ua_rows_decode_mut_dev(ua_ctx *, const ua_drowmut *, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -529,6 +623,19 @@ int ua_rows_union(ua_ctx *, const uint64_t *vals /* host */, uint64_t total,
 int ua_rows_decode(ua_ctx *, const ua_pack *const *packs, uint64_t n_rows,
                    const uint64_t *after, const int32_t *first, uint64_t *out_vals,
                    uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_total);
+/* The handleUidPostings loop over lists with mutable layers as ONE call: host
+ * form of ua_rows_decode_mut_dev (since v17), same semantics (List.iterate's
+ * merge, then x > after[r], then first[r]), same capacity rule and checks.
+ * packs[r] is row r's pack (NULL = a row without blocks); mut_uids, mut_ops
+ * and row_mut_base (host [n_rows+1], n_mut = row_mut_base[n_rows]; NULL = no
+ * mutation at all, which is ua_rows_decode) are host arrays; so are after,
+ * first and the outputs, as for ua_rows_decode. */
+int ua_rows_decode_mut(ua_ctx *, const ua_pack *const *packs, uint64_t n_rows,
+                       const uint64_t *mut_uids, const uint8_t *mut_ops,
+                       const uint64_t *row_mut_base /* host [n_rows+1] */,
+                       const uint64_t *after, const int32_t *first,
+                       uint64_t *out_vals, uint64_t cap_vals,
+                       uint64_t *out_row_offs, uint64_t *out_total);
 /* The handleUidPostings loop with opts.Intersect != nil
  * (posting/list.go:1823-1829: one IntersectCompressedWith per key against
  * q.UidList) as ONE call: host form of ua_rows_intersect_packed_dev (since v16), same semantics
