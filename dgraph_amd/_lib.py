@@ -129,6 +129,23 @@ class UaDRowMut(C.Structure):
     ]
 
 
+class UaDRowEnc(C.Structure):
+    _fields_ = [
+        ("vals", C.c_void_p),
+        ("row_offs", C.c_void_p),
+        ("n_rows", _u64),
+        ("total", _u64),
+        ("block_size", _u64),
+        ("bases", C.c_void_p),
+        ("num_uids", C.c_void_p),
+        ("delta_offs", C.c_void_p),
+        ("cap_blocks", _u64),
+        ("deltas", C.c_void_p),
+        ("cap_deltas", _u64),
+        ("row_block_base", C.c_void_p),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -219,6 +236,11 @@ def lib():
             L.ua_rows_decode_mut.argtypes = [
                 C.c_void_p, C.POINTER(C.POINTER(UaPack)), _u64, _u64p, _u8p, _u64p, _u64p,
                 C.POINTER(C.c_int32), _u64p, _u64, _u64p, _u64p]
+        if L.ua_version() >= 18:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_rows_encode_dev.argtypes = [C.c_void_p, C.POINTER(UaDRowEnc), _u64p, _u64p]
+            L.ua_rows_encode.argtypes = [
+                C.c_void_p, _u64p, _u64p, _u64, _u64, _u64p, _u32p, _u64p, _u64, _u8p, _u64,
+                _u64p, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

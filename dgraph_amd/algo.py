@@ -643,6 +643,85 @@ class Engine:
                      blob[:max(db.value, 1)], int(block_size), n) if k else \
             DPack(bases[:0], nums[:0], offs[:1], blob[:1], int(block_size), 0)
 
+    def encode_rows(self, vals, row_offs, block_size=256, count_only=False, out=None,
+                    row_block_base=None):
+        """A CSR UID matrix into a fan-out of UidPacks in ONE call
+        (ua_rows_encode_dev): one codec.Encoder{BlockSize} per row
+        (codec.go:57-136), as List.encode (posting/list.go:1609-1664) and the
+        bulk reducer (dgraph/cmd/bulk/reduce.go:811-861) run it per key.  vals
+        (rows concatenated, each strictly ascending) and row_offs (n_rows + 1)
+        are CUDA int64 tensors holding u64 bits.  Makes a count-only call, an
+        exact allocation and a full call; out = (bases int64, num_uids int32,
+        delta_offs int64, deltas int8) skips the first (short buffers raise
+        ValueError with the required sizes).  Returns the arena decode_rows,
+        intersect_rows and decode_rows_mut take (a DPack with pbb, _pbb_dev
+        and pack_totals); with count_only (n_blocks, deltas_bytes,
+        row_block_base) and nothing encoded."""
+        import torch
+        from dgraph_amd._lib import UaDRowEnc
+        dev = vals.device
+        total = vals.numel()
+        n_rows = row_offs.numel() - 1
+        if n_rows < 0:
+            raise ValueError("row_offs needs n_rows + 1 entries")
+        if row_block_base is None:
+            row_block_base = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        if row_block_base.numel() < n_rows + 1:
+            raise ValueError(f"row_block_base capacity {row_block_base.numel()} < "
+                             f"required {n_rows + 1}")
+        d = UaDRowEnc()
+        d.vals = vals.data_ptr() if total else None
+        d.row_offs = row_offs.data_ptr()
+        d.n_rows = n_rows
+        d.total = total
+        d.block_size = block_size
+        d.row_block_base = row_block_base.data_ptr()
+        nb, db = _u64(), _u64()
+
+        def call(bufs):
+            if bufs is None:
+                d.bases = d.num_uids = d.delta_offs = d.deltas = None
+                d.cap_blocks = d.cap_deltas = 0
+            else:
+                bases, nums, offs, blob = bufs
+                if offs.numel() < 1 or not bases.numel() or not nums.numel() or \
+                        not blob.numel():
+                    raise ValueError("every pack buffer needs at least one element")
+                d.bases, d.num_uids = bases.data_ptr(), nums.data_ptr()
+                d.delta_offs, d.deltas = offs.data_ptr(), blob.data_ptr()
+                d.cap_blocks = min(bases.numel(), nums.numel(), offs.numel() - 1)
+                d.cap_deltas = blob.numel()
+            rc = lib().ua_rows_encode_dev(self._ctx, C.byref(d), C.byref(nb), C.byref(db))
+            if rc == 3 and bufs is not None and (nb.value > d.cap_blocks or
+                                                 db.value > d.cap_deltas):
+                raise ValueError(f"pack buffers hold {d.cap_blocks} blocks / {d.cap_deltas} "
+                                 f"bytes < required {nb.value} / {db.value}")
+            check(rc)
+
+        if count_only or out is None:
+            call(None)
+            if count_only:
+                return nb.value, db.value, row_block_base[:n_rows + 1]
+            k, nbytes = nb.value, db.value
+            out = (torch.empty(max(k, 1), dtype=torch.int64, device=dev),
+                   torch.empty(max(k, 1), dtype=torch.int32, device=dev),
+                   torch.empty(k + 1, dtype=torch.int64, device=dev),
+                   torch.empty(max(nbytes, 1), dtype=torch.int8, device=dev))
+        call(out)
+        k = nb.value
+        bases, nums, offs, blob = out
+        return RowArena(bases[:k], nums[:k], offs[:k + 1], blob[:max(db.value, 1)],
+                        int(block_size), total, row_block_base[:n_rows + 1],
+                        row_offs[:n_rows + 1])
+
+    def rollup_rows(self, dpb, mut_uids, mut_ops, row_mut_base, block_size=256):
+        """A batched rollup of REF-only lists: List.encode over List.iterate
+        (posting/list.go:1609-1664) for every row of an arena, i.e.
+        decode_rows_mut with after = first = 0, then encode_rows.  Takes
+        decode_rows_mut's arguments and returns encode_rows' arena."""
+        vals, row_offs = self.decode_rows_mut(dpb, mut_uids, mut_ops, row_mut_base)
+        return self.encode_rows(vals, row_offs, block_size)
+
     # ---- packed compositions (algo/packed.go) ----
     def merge_sorted_packed(self, lists, block_size=256):
         """algo.MergeSortedPacked (packed.go:222): dedup k-way union, packed
@@ -803,6 +882,32 @@ class DPack:
         pk.deltas = self.deltas.data_ptr()
         pk.total_uids = self.total_uids
         return pk
+
+
+class RowArena(DPack):
+    """Engine.encode_rows' result: the flat block arena of a fan-out, as
+    upload_pack_batch builds it from host packs.  The row boundaries stay on
+    the device (_pbb_dev); their host copies pbb and pack_totals, which the
+    row decoders size their outputs from, are fetched on first use."""
+
+    def __init__(self, bases, num_uids, delta_offs, deltas, block_size, total_uids,
+                 pbb_dev, row_offs):
+        super().__init__(bases, num_uids, delta_offs, deltas, block_size, total_uids)
+        self._pbb_dev = pbb_dev
+        self._row_offs = row_offs
+        self._pbb = self._totals = None
+
+    @property
+    def pbb(self):
+        if self._pbb is None:
+            self._pbb = self._pbb_dev.cpu().numpy().view(np.uint64)
+        return self._pbb
+
+    @property
+    def pack_totals(self):
+        if self._totals is None:
+            self._totals = np.diff(self._row_offs.cpu().numpy().view(np.uint64)).tolist()
+        return self._totals
 
 
 # ---- host-side codec (product encoder; codec.Encode restated in C++) ----
@@ -1017,6 +1122,47 @@ def row_lengths_mut(engine, packs, muts, after=0):
     Returns a host uint64 array of len(packs) lengths."""
     _, offs = _rows_decode_mut_host(engine, packs, muts, after, 0, True)
     return np.diff(offs)
+
+
+def encode_rows(engine, rows, block_size=256):
+    """codec.Encode of every list of a population as ONE call (ua_rows_encode):
+    the per-key encoders of List.encode (posting/list.go:1609-1664) and of the
+    bulk reducer (dgraph/cmd/bulk/reduce.go:811-861).  rows: sequences of
+    strictly ascending uids.  Returns one encode_flat-shaped tuple per row."""
+    n = len(rows)
+    rows = [_np_u64(r).ravel() for r in rows]
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([r.size for r in rows], dtype=np.uint64)
+    vals = np.ascontiguousarray(np.concatenate(rows)) if n else np.empty(0, np.uint64)
+    rbb = np.empty(n + 1, dtype=np.uint64)
+    nb, db = _u64(), _u64()
+    u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    check(lib().ua_rows_encode(engine._ctx, _hptr(vals), _hptr(offs), n, block_size, None,
+                               None, None, 0, None, 0, _hptr(rbb), C.byref(nb), C.byref(db)))
+    k = nb.value
+    bases = np.empty(max(k, 1), dtype=np.uint64)
+    nums = np.empty(max(k, 1), dtype=np.uint32)
+    doffs = np.empty(k + 1, dtype=np.uint64)
+    blob = np.empty(max(db.value, 1), dtype=np.uint8)
+    check(lib().ua_rows_encode(engine._ctx, _hptr(vals), _hptr(offs), n, block_size,
+                               _hptr(bases), nums.ctypes.data_as(u32p), _hptr(doffs), k,
+                               blob.ctypes.data_as(u8p), db.value, _hptr(rbb), C.byref(nb),
+                               C.byref(db)))
+    out = []
+    for r in range(n):
+        b0, b1 = int(rbb[r]), int(rbb[r + 1])
+        y0, y1 = int(doffs[b0]), int(doffs[b1])
+        out.append((bases[b0:b1], nums[b0:b1], doffs[b0:b1 + 1] - np.uint64(y0),
+                    blob[y0:y1], int(rows[r].size)))
+    return out
+
+
+def rollup_rows(engine, packs, muts, block_size=256):
+    """A batched rollup of REF-only lists: List.encode over List.iterate
+    (posting/list.go:1609-1664) per list, i.e. uid_matrix_mut with after =
+    first = 0, then encode_rows.  Returns one encode_flat-shaped tuple per
+    row."""
+    return encode_rows(engine, uid_matrix_mut(engine, packs, muts), block_size)
 
 
 def uid_matrix_intersect(engine, packs, shared, after=0):

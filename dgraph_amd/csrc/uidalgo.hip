@@ -3156,6 +3156,348 @@ __global__ __launch_bounds__(UA_BLOCK) void k_rows_offs(
     out_row_offs[r] = acc;
 }
 
+/* ==================== kernels: CSR UID matrix -> fan-out of UidPacks ====================
+ * The inverse of the row decoders: every row of a CSR matrix
+ * through codec.Encoder{BlockSize} (codec.go:57-136) in one call, into the flat
+ * block arena the row decoders read.  The geometry is the row filter's: tiles
+ * are cut over the FLAT element array, element e of a tile is lane e % 64 of
+ * wave-step e / 64, so ballot word q covers elements [64q, 64q + 64) in order
+ * and row lengths or block counts cannot unbalance the grid.
+ *
+ * Every element knows from O(1) state what it contributes:
+ *   hard(i)  a row starts at i, or the upper 32 bits change from i - 1 to i;
+ *   h(i)     the last hard index <= i (in the tile, else the tile's carry-in);
+ *   p(i)     (i - h(i)) mod max(block_size, 1), its position in its block;
+ *   start(i) p(i) == 0;  last(i) = start(i + 1) or i + 1 == total.
+ * Bytes are attributed to elements so that a tile's bytes are one contiguous
+ * range of the blob: element p >= 1 owns its delta (1-4 bytes), the control
+ * byte of its group when (p - 1) % 4 == 0, and, when it is last, the group's
+ * 3 - (p - 1) % 4 zero pads; a one-uid block's element owns the all-zero group
+ * (5 bytes).  The count and the write pass are ONE template, so the write pass
+ * stores exactly what the count pass counted. */
+
+#define UA_RENC_LDS (5 * UA_RTILE + 3 + 16 + 13) /* tile bytes + alignment shift, 16-multiple */
+/* Per element: 5 (one-uid block), or at most 4 + 1 + 3 = 8 (a 4-byte delta
+ * that opens a group and ends the block).  A whole block of c >= 2 uids in g
+ * groups is 5g + 3(c - 1) <= 4.25c bytes.  Only the tail of a block cut by the
+ * tile's lower edge can exceed 5 per element: full groups cost 17 per 4, and
+ * a last partial group of j elements 5 + 3j against 5j, +3 at j = 1.  So a
+ * tile holds at most 5 * UA_RTILE + 3 bytes, placed behind a shift < 16. */
+static_assert(UA_RENC_LDS >= 5 * UA_RTILE + 3 + 15 && UA_RENC_LDS % 16 == 0,
+              "k_rowenc: LDS holds a tile's worst-case bytes behind the alignment shift");
+static_assert(UA_RTILE == UA_RWORDS * 64 && UA_RSTEPS * (UA_BLOCK / 64) == UA_RWORDS,
+              "k_rowenc: ballot word q covers elements [64q, 64q + 64)");
+
+/* one thread per row: a non-empty row sets the bit of its (clamped) start.
+ * The bitmap has one spare word past the last tile for the halo bit. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowenc_rowbits(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total,
+    unsigned long long *__restrict__ rowbits) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    u64 a = row_offs[r], b = row_offs[r + 1];
+    a = a < total ? a : total;
+    b = b < total ? b : total;
+    if (a < b) atomicOr(&rowbits[a >> 6], 1ull << (a & 63)); /* a < total */
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(UA_BLOCK) void k_rowenc(
+    const u64 *__restrict__ vals, u64 total, const u64 *__restrict__ row_offs, u64 n_rows,
+    const u64 *__restrict__ rowbits, u32 eff, /* max(block_size, 1) */
+    u64 *__restrict__ kw, u32 *__restrict__ tile_blocks, u32 *__restrict__ tile_bytes,
+    const u64 *__restrict__ boffs, const u64 *__restrict__ bpart,
+    const u64 *__restrict__ yoffs, const u64 *__restrict__ ypart,
+    u64 *__restrict__ bases, u32 *__restrict__ num_uids, u64 *__restrict__ delta_offs,
+    u64 cap_blocks, u8 *__restrict__ deltas, u64 cap_deltas) {
+    __shared__ u64 s_hard[UA_RWORDS + 1];  /* [UA_RWORDS] bit 0: hard(t0 + UA_RTILE) */
+    __shared__ u64 s_start[UA_RWORDS + 1]; /* [UA_RWORDS] bit 0: last(t0 + UA_RTILE - 1) */
+    __shared__ int s_hprev[UA_RWORDS];     /* last hard element below word q, or -1 */
+    __shared__ u32 s_bpre[UA_RWORDS], s_ypre[UA_RWORDS], s_ysum[UA_RWORDS];
+    __shared__ u32 s_r0;                   /* (t0 - rs) mod eff: the carry-in position */
+    __shared__ __attribute__((aligned(16))) u8 s_bytes[WRITE ? UA_RENC_LDS : 16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 tile = blockIdx.x;
+    const u64 t0 = tile * UA_RTILE;
+
+    /* ---- loads, hard flags ---- */
+    u64 v[UA_RSTEPS], pv[UA_RSTEPS];
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int q = s * (UA_BLOCK / 64) + wv;
+        u64 i = t0 + (u64)s * UA_BLOCK + tid;
+        bool in = i < total;
+        v[s] = in ? vals[i] : 0;
+        pv[s] = (in && i > 0) ? vals[i - 1] : 0;
+        u64 rb = rowbits[tile * UA_RWORDS + q]; /* wave-uniform address */
+        bool hard = in && (i == 0 || ((rb >> lane) & 1) || ((v[s] ^ pv[s]) >> 32) != 0);
+        u64 w = __ballot(hard);
+        if (lane == 0) s_hard[q] = w;
+    }
+    if (tid == 0) { /* the element after the tile: its hard flag ends a block here */
+        u64 i = t0 + UA_RTILE;
+        bool hard = false;
+        if (i < total)
+            hard = (rowbits[(tile + 1) * UA_RWORDS] & 1) || ((vals[i] ^ vals[i - 1]) >> 32) != 0;
+        s_hard[UA_RWORDS] = hard ? 1 : 0;
+    }
+
+    /* ---- carry-in (wave 0, wave-uniform): the run start of element t0 ----
+     * The row holding t0 starts at the last row_offs entry <= t0; inside it the
+     * run starts at the first value with t0's upper 32 bits.  Both searches
+     * stay inside their arrays whatever the data; rs is clamped into [0, t0]. */
+    if (wv == 0) {
+        u64 idx = d_wave_lower_bound(row_offs, n_rows + 1, t0 + 1, lane); /* first > t0 */
+        u64 rstart = idx ? row_offs[idx - 1] : 0;
+        rstart = rstart < t0 ? rstart : t0;
+        u64 key = (vals[t0] >> 32) << 32; /* t0 < total: the grid has no empty tile */
+        u64 rs = rstart + d_wave_lower_bound(vals + rstart, t0 - rstart, key, lane);
+        rs = __builtin_amdgcn_readfirstlane((u32)rs) |
+             ((u64)__builtin_amdgcn_readfirstlane((u32)(rs >> 32)) << 32);
+        if (lane == 0) s_r0 = (u32)((t0 - rs) % eff);
+    }
+    __syncthreads();
+
+    /* ---- last hard element below each word (wave 0) ---- */
+    if (wv == 0) {
+        u64 w = lane < UA_RWORDS ? s_hard[lane] : 0;
+        int last = w ? lane * 64 + 63 - __clzll((long long)w) : -1;
+        int run = last; /* inclusive prefix max */
+#pragma unroll
+        for (int o = 1; o < UA_RWORDS; o <<= 1) {
+            int x = __shfl_up(run, o);
+            if (lane >= o) run = run > x ? run : x;
+        }
+        int excl = __shfl_up(run, 1);
+        if (lane < UA_RWORDS) s_hprev[lane] = lane ? excl : -1;
+    }
+    __syncthreads();
+
+    /* ---- positions, block starts ---- */
+    const u32 r0 = s_r0;
+    u32 pos[UA_RSTEPS];
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int q = s * (UA_BLOCK / 64) + wv;
+        const int e = q * 64 + lane;
+        u64 below = s_hard[q] & ((lane == 63) ? ~0ull : ((2ull << lane) - 1)); /* <= lane */
+        int h = below ? q * 64 + 63 - __clzll((long long)below) : s_hprev[q];
+        pos[s] = (h >= 0) ? (u32)(e - h) % eff : (r0 + (u32)e) % eff;
+        bool in = t0 + (u64)e < total;
+        u64 w = __ballot(in && pos[s] == 0);
+        if (lane == 0) s_start[q] = w;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        /* does a block start right after the tile?  Then element UA_RTILE - 1 is last. */
+        u64 i = t0 + UA_RTILE;
+        bool st = true; /* i >= total: the final element is last */
+        if (i < total && !(s_hard[UA_RWORDS] & 1)) {
+            int hl = s_hard[UA_RWORDS - 1]
+                         ? (UA_RWORDS - 1) * 64 + 63 - __clzll((long long)s_hard[UA_RWORDS - 1])
+                         : s_hprev[UA_RWORDS - 1];
+            u32 p = (hl >= 0) ? (u32)(UA_RTILE - hl) % eff : (r0 + (u32)UA_RTILE) % eff;
+            st = (p == 0);
+        }
+        s_start[UA_RWORDS] = st ? 1 : 0;
+    }
+    __syncthreads();
+
+    /* ---- bytes per element, in-word prefix ---- */
+    u32 blen[UA_RSTEPS], yin[UA_RSTEPS]; /* own bytes; exclusive prefix in the word */
+    u32 dl[UA_RSTEPS];
+    u32 meta[UA_RSTEPS]; /* bit0 in, bit1 start, bit2 last */
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int q = s * (UA_BLOCK / 64) + wv;
+        const int e = q * 64 + lane;
+        const u64 i = t0 + (u64)e;
+        const bool in = i < total;
+        const bool st = (s_start[q] >> lane) & 1;
+        /* the next element's start bit; past total every bit is 0, so test the index */
+        bool nx = (lane == 63) ? (s_start[q + 1] & 1) : ((s_start[q] >> (lane + 1)) & 1);
+        const bool last = in && (nx || i + 1 >= total);
+        const u32 p = pos[s];
+        u32 d = (u32)(v[s] - pv[s]);
+        u32 n = 0;
+        if (in) {
+            if (p == 0) {
+                n = last ? 5 : 0;
+            } else {
+                u32 k = (p - 1) & 3;
+                n = 1 + (d > 0xffu) + (d > 0xffffu) + (d > 0xffffffu) + (k == 0 ? 1 : 0) +
+                    (last ? 3 - k : 0);
+            }
+        }
+        dl[s] = d;
+        blen[s] = n;
+        meta[s] = (u32)in | ((u32)st << 1) | ((u32)last << 2);
+        u32 incl = n;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            u32 x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        yin[s] = incl - n;
+        if (lane == 63) s_ysum[q] = incl;
+    }
+    __syncthreads();
+
+    /* ---- per-word prefixes of block starts and bytes (wave 0) ---- */
+    if (wv == 0) {
+        u32 cb = lane < UA_RWORDS ? (u32)__popcll(s_start[lane]) : 0;
+        u32 cy = lane < UA_RWORDS ? s_ysum[lane] : 0;
+        u32 ib = cb, iy = cy;
+#pragma unroll
+        for (int o = 1; o < UA_RWORDS; o <<= 1) {
+            u32 x = __shfl_up(ib, o), y = __shfl_up(iy, o);
+            if (lane >= o) {
+                ib += x;
+                iy += y;
+            }
+        }
+        if (lane < UA_RWORDS) {
+            s_bpre[lane] = ib - cb;
+            s_ypre[lane] = iy - cy;
+        }
+        if (!WRITE) {
+            if (lane < UA_RWORDS) kw[tile * UA_RWORDS + lane] = s_start[lane];
+            if (lane == UA_RWORDS - 1) {
+                tile_blocks[tile] = ib;
+                tile_bytes[tile] = iy;
+            }
+        }
+    }
+    if (!WRITE) return;
+    __syncthreads();
+
+    /* ---- write pass: headers from the elements, bytes through LDS ---- */
+    const u64 bbase = d_off(boffs, bpart, tile);
+    const u64 ybase = d_off(yoffs, ypart, tile);
+    const u32 ytot = s_ypre[UA_RWORDS - 1] + s_ysum[UA_RWORDS - 1];
+    const u32 shift = (u32)(((uintptr_t)deltas + ybase) & 15);
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int q = s * (UA_BLOCK / 64) + wv;
+        const bool in = meta[s] & 1, st = (meta[s] >> 1) & 1, last = (meta[s] >> 2) & 1;
+        const u32 p = pos[s];
+        const u32 yo = s_ypre[q] + yin[s];
+        /* inclusive block rank: a block begun in an earlier tile is bbase - 1 */
+        u32 rk = s_bpre[q] + (u32)__popcll(s_start[q] & ((lane == 63) ? ~0ull : ((2ull << lane) - 1)));
+        u64 b = bbase + rk - 1; /* wraps past cap_blocks only on malformed input */
+        if (in && b < cap_blocks) {
+            if (st) {
+                bases[b] = v[s];
+                delta_offs[b] = ybase + yo;
+            }
+            if (last) num_uids[b] = p + 1;
+        }
+        if (in && blen[s] && shift + yo + blen[s] <= UA_RENC_LDS) {
+            u8 *o = s_bytes + shift + yo;
+            if (p == 0) { /* one-uid block: the all-zero group */
+#pragma unroll
+                for (int k = 0; k < 5; k++) o[k] = 0;
+            } else {
+                const u32 k = (p - 1) & 3;
+                if (k == 0) o++; /* the control byte is assembled below */
+                u32 d = dl[s];
+                *o++ = (u8)d;
+                if (d > 0xffu) *o++ = (u8)(d >> 8);
+                if (d > 0xffffu) *o++ = (u8)(d >> 16);
+                if (d > 0xffffffu) *o++ = (u8)(d >> 24);
+                if (last)
+                    for (u32 z = k; z < 3; z++) *o++ = 0;
+            }
+        }
+    }
+    __syncthreads();
+    /* control bytes: the group's opener ORs in its followers' length codes.
+     * Followers are the next up-to-3 elements of the same block; they may lie
+     * in the next tile, which is why the opener reads them from global. */
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int q = s * (UA_BLOCK / 64) + wv;
+        const int e = q * 64 + lane;
+        const u64 i = t0 + (u64)e;
+        const bool in = meta[s] & 1, last = (meta[s] >> 2) & 1;
+        const u32 p = pos[s];
+        const u32 yo = s_ypre[q] + yin[s];
+        if (in && p != 0 && ((p - 1) & 3) == 0 && shift + yo < UA_RENC_LDS) {
+            u32 d = dl[s];
+            u32 tag = (d > 0xffu) + (d > 0xffffu) + (d > 0xffffffu);
+            /* followers j = 1..3 exist while the block goes on: no start bit at
+             * i + j, i + j < total, and p + j < eff */
+            bool go = !last;
+            u64 prev = v[s];
+            for (u32 j = 1; j < 4 && go; j++) {
+                u64 ij = i + j;
+                if (ij >= total || p + j >= eff) break;
+                u64 x = vals[ij];
+                bool hardj;
+                if (e + (int)j < UA_RTILE) {
+                    hardj = (s_start[(e + j) >> 6] >> ((e + j) & 63)) & 1;
+                } else { /* past the tile: its row bit and 32-MSB test */
+                    hardj = ((rowbits[ij >> 6] >> (ij & 63)) & 1) || ((x ^ prev) >> 32) != 0;
+                }
+                if (hardj) break;
+                u32 dj = (u32)(x - prev);
+                tag |= (u32)((dj > 0xffu) + (dj > 0xffffu) + (dj > 0xffffffu)) << (2 * j);
+                prev = x;
+            }
+            s_bytes[shift + yo] = (u8)tag;
+        }
+    }
+    __syncthreads();
+    /* copy-out: [ybase, ybase + ytot) clipped to cap_deltas; 16-byte stores
+     * for the chunks that lie whole inside the range, bytes for the edges */
+    u64 yend = ybase + ytot;
+    if (yend > cap_deltas) yend = cap_deltas;
+    if (ybase >= yend) return;
+    const u32 nby = (u32)(yend - ybase);
+    u32 nlds = shift + nby;
+    if (nlds > UA_RENC_LDS) nlds = UA_RENC_LDS;
+    u8 *gbase = deltas + ybase - shift; /* 16-byte aligned; [shift, nlds) is ours */
+    const u32 c0 = shift ? 1 : 0, c1 = nlds / 16; /* whole chunks [c0, c1) */
+    for (u32 cidx = c0 + tid; cidx < c1; cidx += UA_BLOCK)
+        *(uint4 *)(gbase + 16 * cidx) = *(const uint4 *)(s_bytes + 16 * cidx);
+    if (shift) {
+        u32 hend = nlds < 16 ? nlds : 16;
+        for (u32 k = shift + tid; k < hend; k += UA_BLOCK) gbase[k] = s_bytes[k];
+    }
+    if (16 * c1 < nlds && !(shift && c1 == 0)) /* c1 == 0 behind a shift: the head was all */
+        for (u32 k = 16 * c1 + tid; k < nlds; k += UA_BLOCK) gbase[k] = s_bytes[k];
+}
+
+/* One thread per row boundary, k_rows_offs' arithmetic over the block-start
+ * words: the blocks before flat position pos are the tile's scanned base plus
+ * the start bits below pos.  Thread n_rows takes pos = total whatever
+ * row_offs says, so row_block_base[n_rows] is the block count; it also
+ * publishes both sizes and closes delta_offs. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rowenc_rows(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total, u64 ntiles,
+    const u64 *__restrict__ kw, const u64 *__restrict__ boffs, const u64 *__restrict__ bpart,
+    const u64 *__restrict__ yoffs, const u64 *__restrict__ ypart,
+    u64 *__restrict__ row_block_base, u64 *__restrict__ delta_offs, u64 cap_blocks,
+    u64 *__restrict__ sizes) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    u64 pos = (r == n_rows) ? total : row_offs[r];
+    pos = pos < total ? pos : total;
+    u64 t = pos / UA_RTILE; /* == ntiles only with rem == 0: the scans have that entry */
+    u32 rem = (u32)(pos % UA_RTILE);
+    u64 acc = d_off(boffs, bpart, t);
+    const u64 *tw = kw + t * UA_RWORDS;
+    for (u32 k = 0; k < rem / 64; k++) acc += (u64)__popcll(tw[k]);
+    if (rem & 63) acc += (u64)__popcll(tw[rem / 64] & ((1ull << (rem & 63)) - 1));
+    row_block_base[r] = acc;
+    if (r == n_rows) {
+        u64 db = d_off(yoffs, ypart, ntiles);
+        sizes[0] = acc;
+        sizes[1] = db;
+        if (delta_offs && acc <= cap_blocks) delta_offs[acc] = db;
+    }
+}
+
 /* ==================== host shim ==================== */
 
 static thread_local hipError_t g_last_hip = hipSuccess;
@@ -3205,7 +3547,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 17; }
+extern "C" int ua_version(void) { return 18; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -5425,6 +5767,194 @@ extern "C" int ua_encode_dev(ua_ctx *c, const uint64_t *uids, uint64_t n,
 
     if ((rc = stats_add(c, c->ev[0], c->ev[1]))) return rc;
     c->bytes_algo += 8 * n + (db_off + db_part) + nb * 20;
+    return UA_OK;
+}
+
+/* ---- CSR UID matrix -> fan-out of UidPacks ----
+ * One codec.Encoder{BlockSize} per row (codec.go:57-136, codec.Encode
+ * codec.go:393) for a whole population of lists, as the bulk reducer
+ * (dgraph/cmd/bulk/reduce.go:811-861, count_index.go:133-154) and the rollup
+ * (posting/list.go:1609-1664) run it one key after another: row bits -> count
+ * -> two tile scans -> row bases (-> write), one sync, two u64 back to the
+ * host.  The argument checks come before c is touched. */
+extern "C" int ua_rows_encode_dev(ua_ctx *c, const ua_drowenc *d, uint64_t *n_blocks,
+                                  uint64_t *deltas_bytes) {
+    if (!c || !d || !n_blocks || !deltas_bytes || !d->row_block_base) return UA_ERR_INVALID;
+    const u64 total = d->total, n_rows = d->n_rows;
+    if (total && !d->vals) return UA_ERR_INVALID;
+    if (n_rows && !d->row_offs) return UA_ERR_INVALID;
+    if (n_rows == 0 && total != 0) return UA_ERR_INVALID;
+    if (d->block_size > UA_MAX_BLOCK_UIDS) return UA_ERR_INVALID;
+    /* the tile grid and the row grids are u32 block counts; a tile's counts
+     * (<= UA_RTILE blocks, <= 5 * UA_RTILE + 3 bytes) always fit the u32 scan */
+    if (total >= ((u64)UA_RTILE << 31) || n_rows >= ((u64)UA_BLOCK << 31))
+        return UA_ERR_INVALID;
+    const int n_null = !d->bases + !d->num_uids + !d->delta_offs + !d->deltas;
+    if (n_null != 0 && n_null != 4) return UA_ERR_INVALID;
+    const bool count_only = (n_null == 4);
+    if (count_only && (d->cap_blocks || d->cap_deltas)) return UA_ERR_INVALID;
+    if (d->cap_blocks >= ((u64)1 << 60)) return UA_ERR_INVALID; /* byte sizes below stay in u64 */
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
+    const struct {
+        const void *p;
+        size_t bytes;
+    } rg[] = {{d->vals, total * sizeof(u64)},
+              {d->row_offs, d->row_offs ? ro_bytes : 0},
+              {d->row_block_base, ro_bytes},
+              {d->bases, d->cap_blocks * sizeof(u64)},
+              {d->num_uids, d->cap_blocks * sizeof(u32)},
+              {d->delta_offs, count_only ? 0 : (d->cap_blocks + 1) * sizeof(u64)},
+              {d->deltas, d->cap_deltas}};
+    const int n_rg = (int)(sizeof(rg) / sizeof(rg[0]));
+    for (int a = 2; a < n_rg; a++) /* every output against the inputs and the other outputs */
+        for (int b = 0; b < a; b++)
+            if (rg[a].p && rg[b].p && ranges_overlap(rg[a].p, rg[a].bytes, rg[b].p, rg[b].bytes))
+                return UA_ERR_INVALID;
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    if (total == 0) { /* every row is empty: zero offsets, no launch */
+        HIP_TRY(hipMemsetAsync(d->row_block_base, 0, ro_bytes, c->stream));
+        if (!count_only) HIP_TRY(hipMemsetAsync(d->delta_offs, 0, sizeof(u64), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->bytes_algo += 16 * (n_rows + 1);
+        *n_blocks = 0;
+        *deltas_bytes = 0;
+        return UA_OK;
+    }
+    const u64 ntiles = (total + UA_RTILE - 1) / UA_RTILE;
+    const u64 nchunks = scan_chunks(ntiles + 1);
+    const size_t ycnt_bytes = align16((ntiles + 1) * sizeof(u32));
+    const size_t yoffs_bytes = align16((ntiles + 1) * sizeof(u64));
+    const size_t ypart_bytes = align16((nchunks + 1) * sizeof(u64));
+    const size_t bits_bytes = (size_t)(ntiles * UA_RWORDS + 1) * sizeof(u64);
+    int rc;
+    if ((rc = ws_reserve(c, WS_SCRATCH_A, bits_bytes))) return rc;
+    if ((rc = ws_reserve(c, WS_RKW, (size_t)ntiles * UA_RWORDS * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_TCNT, (size_t)(ntiles + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (size_t)(ntiles + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_KLEN, ycnt_bytes + yoffs_bytes + ypart_bytes + 2 * sizeof(u64))))
+        return rc;
+    u64 *d_bits = (u64 *)c->ws[WS_SCRATCH_A];
+    u64 *d_kw = (u64 *)c->ws[WS_RKW];
+    u32 *d_bcnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_boffs = (u64 *)c->ws[WS_TOFF];
+    u32 *d_ycnt = (u32 *)c->ws[WS_KLEN];
+    u64 *d_yoffs = (u64 *)((u8 *)c->ws[WS_KLEN] + ycnt_bytes);
+    u64 *d_ypart = (u64 *)((u8 *)d_yoffs + yoffs_bytes);
+    u64 *d_sizes = (u64 *)((u8 *)d_ypart + ypart_bytes);
+    const u32 eff = d->block_size ? (u32)d->block_size : 1;
+    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+
+    HIP_TRY(hipMemsetAsync(d_bits, 0, bits_bytes, c->stream));
+    /* one extra zero count each: d_off(ntiles) is the grand total */
+    HIP_TRY(hipMemsetAsync(d_bcnt + ntiles, 0, sizeof(u32), c->stream));
+    HIP_TRY(hipMemsetAsync(d_ycnt + ntiles, 0, sizeof(u32), c->stream));
+    hipLaunchKernelGGL(k_rowenc_rowbits, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                       d->row_offs, n_rows, total, (unsigned long long *)d_bits);
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_rowenc<false>, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                       d->vals, total, d->row_offs, n_rows, d_bits, eff, d_kw, d_bcnt, d_ycnt,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (u64)0,
+                       nullptr, (u64)0);
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    if ((rc = ws_scan(c, d_bcnt, ntiles + 1, d_boffs))) return rc;
+    const u64 *d_bpart = (const u64 *)c->ws[WS_PARTIAL];
+    enqueue_scan(d_ycnt, ntiles + 1, d_yoffs, d_ypart, nchunks, c->stream);
+    hipLaunchKernelGGL(k_rowenc_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d->row_offs,
+                       n_rows, total, ntiles, d_kw, d_boffs, d_bpart, d_yoffs, d_ypart,
+                       d->row_block_base, d->delta_offs, d->cap_blocks, d_sizes);
+    if (!count_only) {
+        HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+        hipLaunchKernelGGL(k_rowenc<true>, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                           d->vals, total, d->row_offs, n_rows, d_bits, eff, d_kw, d_bcnt,
+                           d_ycnt, d_boffs, d_bpart, d_yoffs, d_ypart, d->bases, d->num_uids,
+                           d->delta_offs, d->cap_blocks, d->deltas, d->cap_deltas);
+        HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    }
+    u64 sizes[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(sizes, d_sizes, sizeof(sizes), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], 7))) return rc;
+    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    c->bytes_algo += 8 * total + 8 * (n_rows + 1) + sizes[1] + 20 * sizes[0] + 8 * (n_rows + 1);
+    *n_blocks = sizes[0];
+    *deltas_bytes = sizes[1];
+    return (!count_only && (sizes[0] > d->cap_blocks || sizes[1] > d->cap_deltas))
+               ? UA_ERR_INVALID
+               : UA_OK;
+}
+
+/* host-pointer form of ua_rows_encode_dev: total is row_offs[n_rows].  Upload,
+ * one device call, download what fits the capacities; count-only with all
+ * four pack outputs NULL. */
+extern "C" int ua_rows_encode(ua_ctx *c, const uint64_t *vals, const uint64_t *row_offs,
+                              uint64_t n_rows, uint64_t block_size, uint64_t *bases,
+                              uint32_t *num_uids, uint64_t *delta_offs, uint64_t cap_blocks,
+                              uint8_t *deltas, uint64_t cap_deltas, uint64_t *row_block_base,
+                              uint64_t *n_blocks, uint64_t *deltas_bytes) {
+    if (!c || !n_blocks || !deltas_bytes || !row_block_base) return UA_ERR_INVALID;
+    if (n_rows && !row_offs) return UA_ERR_INVALID;
+    const u64 total = n_rows ? row_offs[n_rows] : 0;
+    if (total && !vals) return UA_ERR_INVALID;
+    if (block_size > UA_MAX_BLOCK_UIDS) return UA_ERR_INVALID;
+    if (total >= ((u64)UA_RTILE << 31) || n_rows >= ((u64)UA_BLOCK << 31))
+        return UA_ERR_INVALID;
+    const int n_null = !bases + !num_uids + !delta_offs + !deltas;
+    if (n_null != 0 && n_null != 4) return UA_ERR_INVALID;
+    const bool count_only = (n_null == 4);
+    if (count_only && (cap_blocks || cap_deltas)) return UA_ERR_INVALID;
+    if (cap_blocks >= ((u64)1 << 60)) return UA_ERR_INVALID;
+    /* the device never needs more than one block per uid and 5 bytes + 3 per uid */
+    const u64 cb = std::min(cap_blocks, total), cd = std::min(cap_deltas, 5 * total + 3);
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_H* reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    if ((rc = ws_reserve(c, WS_HU, (total + nro) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (nro + cb + cb + 1) * sizeof(u64) + cb * sizeof(u32) + 16)))
+        return rc;
+    if ((rc = ws_reserve(c, WS_HV, cd + 16))) return rc;
+    u64 *d_vals = (u64 *)c->ws[WS_HU], *d_ro = d_vals + total;
+    u64 *d_rbb = (u64 *)c->ws[WS_HOUT], *d_bases = d_rbb + nro, *d_doffs = d_bases + cb;
+    u32 *d_nums = (u32 *)(d_doffs + cb + 1);
+    u8 *d_blob = (u8 *)c->ws[WS_HV];
+    if (total)
+        HIP_TRY(hipMemcpyAsync(d_vals, vals, total * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    if (n_rows)
+        HIP_TRY(hipMemcpyAsync(d_ro, row_offs, nro * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    else
+        HIP_TRY(hipMemsetAsync(d_ro, 0, sizeof(u64), c->stream));
+    ua_drowenc d = {d_vals, d_ro, n_rows, total, block_size,
+                    count_only ? nullptr : d_bases, count_only ? nullptr : d_nums,
+                    count_only ? nullptr : d_doffs, count_only ? 0 : cb,
+                    count_only ? nullptr : d_blob, count_only ? 0 : cd, d_rbb};
+    u64 nb = 0, db = 0;
+    rc = ua_rows_encode_dev(c, &d, &nb, &db);
+    if (rc && rc != UA_ERR_INVALID) return rc;
+    if (rc == UA_ERR_INVALID && nb == 0 && db == 0 && total) return rc; /* rejected */
+    *n_blocks = nb;
+    *deltas_bytes = db;
+    HIP_TRY(hipMemcpyAsync(row_block_base, d_rbb, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    if (!count_only && rc == UA_OK && nb <= cap_blocks && db <= cap_deltas) {
+        if (nb) {
+            HIP_TRY(hipMemcpyAsync(bases, d_bases, nb * sizeof(u64), hipMemcpyDeviceToHost,
+                                   c->stream));
+            HIP_TRY(hipMemcpyAsync(num_uids, d_nums, nb * sizeof(u32), hipMemcpyDeviceToHost,
+                                   c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(delta_offs, d_doffs, (nb + 1) * sizeof(u64),
+                               hipMemcpyDeviceToHost, c->stream));
+        if (db)
+            HIP_TRY(hipMemcpyAsync(deltas, d_blob, db, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!count_only && (nb > cap_blocks || db > cap_deltas)) return UA_ERR_INVALID;
     return UA_OK;
 }
 

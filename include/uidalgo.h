@@ -537,6 +537,77 @@ typedef struct {
 } ua_drowmut;                       /* 16 slots, 128 bytes: n_mut at 96, cap_vals at 112 */
 int ua_rows_decode_mut_dev(ua_ctx *, const ua_drowmut *, uint64_t *out_total);
 
+/* A CSR UID matrix encoded into a fan-out of UidPacks in ONE call: the inverse
+ * of the three row decoders, one stream sync (since v18).  The reference
+ * encodes populations of lists one list after another, one
+ * codec.Encoder{BlockSize} each (codec.go:57-136; codec.Encode, codec.go:393,
+ * is that loop for one list): List.encode in the rollup, one encoder per
+ * split part (posting/list.go:1609-1664), the bulk loader's reduce over every
+ * key of a map shard (dgraph/cmd/bulk/reduce.go:811-861) and its count index
+ * (dgraph/cmd/bulk/count_index.go:133-154).  Here every list is one row.
+ *
+ * Row r's blocks are what codec.Encoder{BlockSize: block_size} yields after
+ * Add of each value of row r in order.  A new block starts at a row start,
+ * wherever the upper 32 bits change, and every block_size uids inside a row's
+ * 32-MSB run (block_size 0 behaves as 1, like ua_encode_dev).  bases[b] is the
+ * block's first uid; its deltas are group-varint groups of four, the last
+ * group zero-padded, and a one-uid block carries one all-zero group.  On every
+ * strictly ascending row the bytes are those of ua_encode and of the oracle's
+ * encoder.  Blocks are laid out in row order: row_block_base[r] is the index
+ * of row r's first block, row_block_base[n_rows] == *n_blocks,
+ * delta_offs[*n_blocks] == *deltas_bytes, and an empty row owns no block.  A
+ * multi-part list (Splits) passes one row per part.  Rows are not
+ * de-duplicated: the bulk reducer's uid == lastUid skip stays with the caller
+ * (ua_rows_union_dev first).
+ *
+ * The output is, unchanged, the arena of ua_rows_decode_dev,
+ * ua_rows_intersect_packed_dev and ua_rows_decode_mut_dev.  Their limit
+ * n_blocks <= 2^24 - 1 is the consumers', not this call's.
+ *
+ * Capacity, by the family's rule: *n_blocks, *deltas_bytes and row_block_base
+ * are always the REQUIRED and complete values, whatever the capacities.  Every
+ * store is bounded by its capacity.  If either requirement exceeds its
+ * capacity and the outputs are not NULL the call returns UA_ERR_INVALID; the
+ * outputs are then unspecified but untouched past the capacities.  Count-only
+ * form: all four pack outputs NULL with both capacities 0; it runs no write
+ * pass and sizes the second call exactly.
+ *
+ * Rejected with UA_ERR_INVALID before the context is touched, nothing
+ * written: a null ctx, desc, n_blocks, deltas_bytes or row_block_base; null
+ * vals with total > 0; null row_offs with n_rows > 0; n_rows == 0 with
+ * total != 0; block_size > 256; some but not all pack outputs NULL, or a NULL
+ * output with a non-zero capacity; any output overlapping an input or another
+ * output; total >= 2^42 or n_rows >= 2^39 (the tile grid, total / 2048, and the
+ * row grid, n_rows / 256, are 32-bit block counts; a tile's counts, at most
+ * 2048 blocks and 5 * 2048 + 3 bytes, always fit the engine's u32 scan);
+ * cap_blocks >= 2^60.  total == 0 is valid: zero offsets and no launch.
+ *
+ * Memory safety does not depend on the data: row_offs entries are clamped to
+ * total; rows that are not ascending or a row_offs that is not monotone give
+ * unspecified packs, never an out-of-range access.  The write pass is the
+ * count pass's code and stores exactly what that counted.
+ *
+ * Stats: 7 launches without the write pass (row bits, count, two scans of two
+ * kernels, row bases) and 8 with it; kernel_ms is the count pass plus the
+ * write pass.  bytes_algorithmic grows by input plus output:
+ * 8*total + 8*(n_rows+1) plus *deltas_bytes + 20*(*n_blocks) + 8*(n_rows+1). */
+typedef struct {
+    const uint64_t *vals;           /* device [total]: rows concatenated */
+    const uint64_t *row_offs;       /* device [n_rows+1], non-decreasing,
+                                     * [0] = 0, [n_rows] = total */
+    uint64_t n_rows, total;
+    uint64_t block_size;            /* <= 256; 0 packs one uid per block */
+    uint64_t *bases;                /* device [cap_blocks] */
+    uint32_t *num_uids;             /* device [cap_blocks] */
+    uint64_t *delta_offs;           /* device [cap_blocks+1] */
+    uint64_t cap_blocks;
+    uint8_t *deltas;                /* device [cap_deltas] */
+    uint64_t cap_deltas;
+    uint64_t *row_block_base;       /* device [n_rows+1], always written */
+} ua_drowenc;                       /* 12 slots, 96 bytes */
+int ua_rows_encode_dev(ua_ctx *, const ua_drowenc *, uint64_t *n_blocks,
+                       uint64_t *deltas_bytes);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -649,6 +720,19 @@ int ua_rows_intersect_packed(ua_ctx *, const ua_pack *const *packs, uint64_t n_r
                              const uint64_t *after, const uint64_t *shared, uint64_t m,
                              uint64_t *out_vals, uint64_t cap_vals,
                              uint64_t *out_row_offs, uint64_t *out_total);
+/* One codec.Encoder{BlockSize} per list over a population of lists
+ * (codec.go:57-136, codec.go:393; posting/list.go:1609-1664;
+ * dgraph/cmd/bulk/reduce.go:811-861, count_index.go:133-154) as ONE call: host
+ * form of ua_rows_encode_dev (since v18), same semantics, capacity rule and
+ * checks.  vals and row_offs are host arrays, total = row_offs[n_rows]; the
+ * five outputs are host arrays with ua_drowenc's capacities (count only: the
+ * four pack outputs NULL, both capacities 0).  On a short capacity
+ * row_block_base and both sizes are still delivered. */
+int ua_rows_encode(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
+                   uint64_t n_rows, uint64_t block_size, uint64_t *bases,
+                   uint32_t *num_uids, uint64_t *delta_offs, uint64_t cap_blocks,
+                   uint8_t *deltas, uint64_t cap_deltas, uint64_t *row_block_base,
+                   uint64_t *n_blocks, uint64_t *deltas_bytes);
 
 #ifdef __cplusplus
 }
