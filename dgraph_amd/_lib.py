@@ -72,61 +72,38 @@ class UaDRows(C.Structure):
     ]
 
 
+# the three pack fan-out -> CSR descriptors share their first nine slots (the
+# block arena, the row boundaries, after, first) and their last three
+_ROW_ARENA = [
+    ("bases", C.c_void_p),
+    ("num_uids", C.c_void_p),
+    ("delta_offs", C.c_void_p),
+    ("deltas", C.c_void_p),
+    ("n_blocks", _u64),
+    ("row_block_base", C.c_void_p),
+    ("n_rows", _u64),
+    ("after", C.c_void_p),
+]
+_ROW_PREFIX = _ROW_ARENA + [("first", C.c_void_p)]
+_ROW_OUT = [
+    ("out_vals", C.c_void_p),
+    ("cap_vals", _u64),
+    ("out_row_offs", C.c_void_p),
+]
+
+
 class UaDRowPacks(C.Structure):
-    _fields_ = [
-        ("bases", C.c_void_p),
-        ("num_uids", C.c_void_p),
-        ("delta_offs", C.c_void_p),
-        ("deltas", C.c_void_p),
-        ("n_blocks", _u64),
-        ("row_block_base", C.c_void_p),
-        ("n_rows", _u64),
-        ("after", C.c_void_p),
-        ("first", C.c_void_p),
-        ("out_vals", C.c_void_p),
-        ("cap_vals", _u64),
-        ("out_row_offs", C.c_void_p),
-    ]
+    _fields_ = _ROW_PREFIX + _ROW_OUT
 
 
-class UaDRowIsect(C.Structure):
-    _fields_ = [
-        ("bases", C.c_void_p),
-        ("num_uids", C.c_void_p),
-        ("delta_offs", C.c_void_p),
-        ("deltas", C.c_void_p),
-        ("n_blocks", _u64),
-        ("row_block_base", C.c_void_p),
-        ("n_rows", _u64),
-        ("after", C.c_void_p),
-        ("reserved", C.c_void_p),
-        ("shared", C.c_void_p),
-        ("m", _u64),
-        ("out_vals", C.c_void_p),
-        ("cap_vals", _u64),
-        ("out_row_offs", C.c_void_p),
-    ]
+class UaDRowIsect(C.Structure):  # slot 8 must stay NULL: this call has no first
+    _fields_ = _ROW_ARENA + [("reserved", C.c_void_p), ("shared", C.c_void_p),
+                             ("m", _u64)] + _ROW_OUT
 
 
 class UaDRowMut(C.Structure):
-    _fields_ = [
-        ("bases", C.c_void_p),
-        ("num_uids", C.c_void_p),
-        ("delta_offs", C.c_void_p),
-        ("deltas", C.c_void_p),
-        ("n_blocks", _u64),
-        ("row_block_base", C.c_void_p),
-        ("n_rows", _u64),
-        ("after", C.c_void_p),
-        ("first", C.c_void_p),
-        ("mut_uids", C.c_void_p),
-        ("mut_ops", C.c_void_p),
-        ("row_mut_base", C.c_void_p),
-        ("n_mut", _u64),
-        ("out_vals", C.c_void_p),
-        ("cap_vals", _u64),
-        ("out_row_offs", C.c_void_p),
-    ]
+    _fields_ = _ROW_PREFIX + [("mut_uids", C.c_void_p), ("mut_ops", C.c_void_p),
+                              ("row_mut_base", C.c_void_p), ("n_mut", _u64)] + _ROW_OUT
 
 
 class UaDRowEnc(C.Structure):

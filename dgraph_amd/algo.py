@@ -338,31 +338,34 @@ class Engine:
         Returns (vals[:total], row_offs), the CSR form filter_rows and
         union_rows take; with count_only vals is empty and row_offs holds
         every key's List.Length (list.go:1345)."""
-        import torch
         from dgraph_amd._lib import UaDRowPacks
+        full = 0 if count_only else int(sum(dpb.pack_totals))
+        # without afters and firsts every row is whole: a short buffer is known now
+        if afters is None and firsts is None and out_vals is not None and not count_only \
+                and out_vals.numel() < full:
+            raise ValueError(f"out_vals capacity {out_vals.numel()} < required {full}")
+        return self._rows_call(lib().ua_rows_decode_dev, UaDRowPacks(), dpb, afters, firsts,
+                               out_vals, out_row_offs, count_only, lambda: full)
+
+    def _rows_arena(self, dpb):
+        """(device, n_rows, n_blocks) of an upload_pack_batch arena; its row
+        boundaries go to the device once and stay with it (_pbb_dev)."""
+        import torch
         dev = dpb.bases.device
         n_rows = len(dpb.pbb) - 1
-        nb = int(dpb.pbb[n_rows])
         if getattr(dpb, "_pbb_dev", None) is None:
             dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
+        return dev, n_rows, int(dpb.pbb[n_rows])
 
-        def per_row(x, np_dt, view_dt, t_dt):
-            if x is None:
-                return None
-            if isinstance(x, torch.Tensor):
-                if x.dtype != t_dt or x.numel() < n_rows:
-                    raise ValueError(f"per-row tensor needs {n_rows} x {t_dt}")
-                return x
-            a = np.asarray(x, dtype=np_dt)
-            a = np.full(n_rows, a, dtype=np_dt) if a.ndim == 0 else np.ascontiguousarray(a)
-            if a.size != n_rows:
-                raise ValueError(f"per-row argument needs {n_rows} entries, got {a.size}")
-            if n_rows == 0:
-                return None
-            return torch.from_numpy(a.view(view_dt)).to(dev)
-
-        t_after = per_row(afters, np.uint64, np.int64, torch.int64)
-        t_first = per_row(firsts, np.int32, np.int32, torch.int32)
+    def _rows_call(self, fn, d, dpb, afters, firsts, out_vals, out_row_offs, count_only, full):
+        """The one path of decode_rows, intersect_rows and decode_rows_mut: a
+        pack fan-out in, a CSR matrix out.  d is the call's descriptor with
+        its own slots filled, fn its device entry, full() the capacity a
+        missing out_vals gets.  firsts is None for a call without first."""
+        import torch
+        dev, n_rows, nb = self._rows_arena(dpb)
+        t_after = _per_row_dev(afters, n_rows, np.uint64, dev)
+        t_first = _per_row_dev(firsts, n_rows, np.int32, dev)
         if out_row_offs is None:
             out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
         if out_row_offs.numel() < n_rows + 1:
@@ -370,13 +373,9 @@ class Engine:
                              f"required {n_rows + 1}")
         cap = 0
         if not count_only:
-            full = int(sum(dpb.pack_totals))
             if out_vals is None:
-                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
+                out_vals = torch.empty(max(full(), 1), dtype=torch.int64, device=dev)
             cap = out_vals.numel()
-            if t_after is None and t_first is None and cap < full:
-                raise ValueError(f"out_vals capacity {cap} < required {full}")
-        d = UaDRowPacks()
         d.bases = dpb.bases.data_ptr()
         d.num_uids = dpb.num_uids.data_ptr()
         d.delta_offs = dpb.delta_offs.data_ptr()
@@ -385,12 +384,13 @@ class Engine:
         d.row_block_base = dpb._pbb_dev.data_ptr()
         d.n_rows = n_rows
         d.after = t_after.data_ptr() if t_after is not None else None
-        d.first = t_first.data_ptr() if t_first is not None else None
+        if t_first is not None:
+            d.first = t_first.data_ptr()
         d.out_vals = None if count_only else out_vals.data_ptr()
         d.cap_vals = cap
         d.out_row_offs = out_row_offs.data_ptr()
         total = _u64()
-        rc = lib().ua_rows_decode_dev(self._ctx, C.byref(d), C.byref(total))
+        rc = fn(self._ctx, C.byref(d), C.byref(total))
         if rc == 3 and not count_only and total.value > cap:
             raise ValueError(f"out_vals capacity {cap} < required {total.value}")
         check(rc)
@@ -416,13 +416,9 @@ class Engine:
         sum(pack_totals) + n_mut."""
         import torch
         from dgraph_amd._lib import UaDRowMut
-        dev = dpb.bases.device
-        n_rows = len(dpb.pbb) - 1
-        nb = int(dpb.pbb[n_rows])
-        if getattr(dpb, "_pbb_dev", None) is None:
-            dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
+        dev, n_rows, _ = self._rows_arena(dpb)
 
-        def dev_arr(x, n, np_dt, view_dt, t_dt, what):
+        def dev_arr(x, n, np_dt, t_dt, what):
             if isinstance(x, torch.Tensor):
                 if x.dtype != t_dt or x.numel() < n:
                     raise ValueError(f"{what} needs {n} x {t_dt}")
@@ -430,58 +426,20 @@ class Engine:
             a = np.ascontiguousarray(np.asarray(x, dtype=np_dt).ravel())
             if a.size != n:
                 raise ValueError(f"{what} needs {n} entries, got {a.size}")
-            return torch.from_numpy(a.view(view_dt)).to(dev) if n else None
-
-        def per_row(x, np_dt, view_dt, t_dt):
-            if x is None:
-                return None
-            if not isinstance(x, torch.Tensor):
-                x = _per_row(x, n_rows, np_dt)[:n_rows]
-            return dev_arr(x, n_rows, np_dt, view_dt, t_dt, "per-row")
+            return _to_dev(a, dev) if n else None
 
         n_mut = mut_uids.numel() if isinstance(mut_uids, torch.Tensor) else len(mut_uids)
-        t_muids = dev_arr(mut_uids, n_mut, np.uint64, np.int64, torch.int64, "mut_uids")
-        t_mops = dev_arr(mut_ops, n_mut, np.uint8, np.uint8, torch.uint8, "mut_ops")
-        t_rmb = dev_arr(row_mut_base, n_rows + 1, np.uint64, np.int64, torch.int64,
-                        "row_mut_base") if n_mut else None
-        t_after = per_row(afters, np.uint64, np.int64, torch.int64)
-        t_first = per_row(firsts, np.int32, np.int32, torch.int32)
-        if out_row_offs is None:
-            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        if out_row_offs.numel() < n_rows + 1:
-            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
-                             f"required {n_rows + 1}")
-        cap = 0
-        if not count_only:
-            if out_vals is None:
-                full = int(sum(dpb.pack_totals)) + n_mut
-                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
-            cap = out_vals.numel()
+        keep = [dev_arr(mut_uids, n_mut, np.uint64, torch.int64, "mut_uids"),
+                dev_arr(mut_ops, n_mut, np.uint8, torch.uint8, "mut_ops")]
         d = UaDRowMut()
-        d.bases = dpb.bases.data_ptr()
-        d.num_uids = dpb.num_uids.data_ptr()
-        d.delta_offs = dpb.delta_offs.data_ptr()
-        d.deltas = dpb.deltas.data_ptr()
-        d.n_blocks = nb
-        d.row_block_base = dpb._pbb_dev.data_ptr()
-        d.n_rows = n_rows
-        d.after = t_after.data_ptr() if t_after is not None else None
-        d.first = t_first.data_ptr() if t_first is not None else None
-        d.mut_uids = t_muids.data_ptr() if n_mut else None
-        d.mut_ops = t_mops.data_ptr() if n_mut else None
-        d.row_mut_base = t_rmb.data_ptr() if n_mut else None
         d.n_mut = n_mut
-        d.out_vals = None if count_only else out_vals.data_ptr()
-        d.cap_vals = cap
-        d.out_row_offs = out_row_offs.data_ptr()
-        total = _u64()
-        rc = lib().ua_rows_decode_mut_dev(self._ctx, C.byref(d), C.byref(total))
-        if rc == 3 and not count_only and total.value > cap:
-            raise ValueError(f"out_vals capacity {cap} < required {total.value}")
-        check(rc)
-        if count_only:
-            return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
-        return out_vals[:total.value], out_row_offs[:n_rows + 1]
+        if n_mut:  # without a layer the three arrays stay NULL: the plain call
+            keep.append(dev_arr(row_mut_base, n_rows + 1, np.uint64, torch.int64,
+                                "row_mut_base"))
+            d.mut_uids, d.mut_ops, d.row_mut_base = (t.data_ptr() for t in keep)
+        return self._rows_call(lib().ua_rows_decode_mut_dev, d, dpb, afters, firsts, out_vals,
+                               out_row_offs, count_only,
+                               lambda: int(sum(dpb.pack_totals)) + n_mut)
 
     def intersect_rows(self, dpb, shared, afters=None, out_vals=None, out_row_offs=None,
                        count_only=False):
@@ -499,56 +457,15 @@ class Engine:
         empty and row_offs holds every key's count under the filter."""
         import torch
         from dgraph_amd._lib import UaDRowIsect
-        dev = dpb.bases.device
-        n_rows = len(dpb.pbb) - 1
-        nb = int(dpb.pbb[n_rows])
         m = shared.numel()
         if shared.dtype != torch.int64:
             raise ValueError("shared needs int64 (u64 bits)")
-        if getattr(dpb, "_pbb_dev", None) is None:
-            dpb._pbb_dev = torch.from_numpy(_np_u64(dpb.pbb).view(np.int64)).to(dev)
-        t_after = None
-        if isinstance(afters, torch.Tensor):
-            if afters.dtype != torch.int64 or afters.numel() < n_rows:
-                raise ValueError(f"per-row tensor needs {n_rows} x {torch.int64}")
-            t_after = afters
-        elif afters is not None:
-            a = _per_row(afters, n_rows, np.uint64)
-            if n_rows:
-                t_after = torch.from_numpy(a.view(np.int64)).to(dev)
-        if out_row_offs is None:
-            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        if out_row_offs.numel() < n_rows + 1:
-            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
-                             f"required {n_rows + 1}")
-        cap = 0
-        if not count_only:
-            if out_vals is None:
-                full = int(sum(min(int(t), m) for t in dpb.pack_totals))
-                out_vals = torch.empty(max(full, 1), dtype=torch.int64, device=dev)
-            cap = out_vals.numel()
         d = UaDRowIsect()
-        d.bases = dpb.bases.data_ptr()
-        d.num_uids = dpb.num_uids.data_ptr()
-        d.delta_offs = dpb.delta_offs.data_ptr()
-        d.deltas = dpb.deltas.data_ptr()
-        d.n_blocks = nb
-        d.row_block_base = dpb._pbb_dev.data_ptr()
-        d.n_rows = n_rows
-        d.after = t_after.data_ptr() if t_after is not None else None
         d.shared = shared.data_ptr() if m else None
         d.m = m
-        d.out_vals = None if count_only else out_vals.data_ptr()
-        d.cap_vals = cap
-        d.out_row_offs = out_row_offs.data_ptr()
-        total = _u64()
-        rc = lib().ua_rows_intersect_packed_dev(self._ctx, C.byref(d), C.byref(total))
-        if rc == 3 and not count_only and total.value > cap:
-            raise ValueError(f"out_vals capacity {cap} < required {total.value}")
-        check(rc)
-        if count_only:
-            return torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]
-        return out_vals[:total.value], out_row_offs[:n_rows + 1]
+        return self._rows_call(lib().ua_rows_intersect_packed_dev, d, dpb, afters, None,
+                               out_vals, out_row_offs, count_only,
+                               lambda: int(sum(min(int(t), m) for t in dpb.pack_totals)))
 
     def intersect_packed_batch(self, dpb, vs, outs=None, afters=None):
         """Batched algo.IntersectCompressedWith: every pack of the fan-out in
@@ -1031,14 +948,44 @@ def _per_row(x, n, dtype):
     return a if n else np.zeros(1, dtype=dtype)
 
 
+def _to_dev(a, dev):
+    """A host array as a device tensor; u64 crosses as its int64 bits."""
+    import torch
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+
+
+def _per_row_dev(x, n, dtype, dev):
+    """A per-row argument of an Engine call as a device tensor: None stays
+    None (= all 0), one value or a sequence goes through _per_row, a CUDA
+    tensor of at least n entries (int64 for u64 bits) passes as it is."""
+    import torch
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        t_dt = torch.int64 if dtype is np.uint64 else torch.int32
+        if x.dtype != t_dt or x.numel() < n:
+            raise ValueError(f"per-row tensor needs {n} x {t_dt}")
+        return x
+    a = _per_row(x, n, dtype)
+    return _to_dev(a, dev) if n else None
+
+
+def _rows_out(n, cap):
+    """Host buffers of a CSR result: cap values (one at least) and n + 1 offsets."""
+    return np.empty(max(cap, 1), dtype=np.uint64), np.empty(n + 1, dtype=np.uint64)
+
+
+def _split_rows(vals, offs):
+    return [vals[int(offs[r]):int(offs[r + 1])] for r in range(len(offs) - 1)]
+
+
 def _rows_decode_host(engine, packs, after, first, count_only):
     n = len(packs)
     ptrs, keep = _host_packs(packs)
     a = _per_row(after, n, np.uint64)
     f = _per_row(first, n, np.int32)
     cap = 0 if count_only else sum(int(p[4]) for p in packs)
-    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
-    out_offs = np.empty(n + 1, dtype=np.uint64)
+    out_vals, out_offs = _rows_out(n, cap)
     total = _u64()
     check(lib().ua_rows_decode(engine._ctx, ptrs, n, _hptr(a),
                                f.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -1055,8 +1002,7 @@ def uid_matrix(engine, packs, after=0, first=0):
     all), then the first `first` of them (or the last -first; 0 all).  packs:
     tuples from encode_flat; after/first: one value or one per row.  Returns
     a list of host uint64 arrays."""
-    out_vals, offs = _rows_decode_host(engine, packs, after, first, False)
-    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(len(packs))]
+    return _split_rows(*_rows_decode_host(engine, packs, after, first, False))
 
 
 def row_lengths(engine, packs, after=0):
@@ -1093,8 +1039,7 @@ def _rows_decode_mut_host(engine, packs, muts, after, first, count_only):
     a = _per_row(after, n, np.uint64)
     f = _per_row(first, n, np.int32)
     cap = 0 if count_only else sum(int(p[4]) for p in packs) + uids.size
-    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
-    out_offs = np.empty(n + 1, dtype=np.uint64)
+    out_vals, out_offs = _rows_out(n, cap)
     total = _u64()
     check(lib().ua_rows_decode_mut(
         engine._ctx, ptrs, n, _hptr(uids) if uids.size else None,
@@ -1112,8 +1057,7 @@ def uid_matrix_mut(engine, packs, muts, after=0, first=0):
     with muts[r], a list of (uid, op) strictly ascending by uid: MUT_DEL
     removes the uid, any other op sets it.  Then uids > after (0 keeps all),
     then first, as in uid_matrix.  Returns a list of host uint64 arrays."""
-    out_vals, offs = _rows_decode_mut_host(engine, packs, muts, after, first, False)
-    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(len(packs))]
+    return _split_rows(*_rows_decode_mut_host(engine, packs, muts, after, first, False))
 
 
 def row_lengths_mut(engine, packs, muts, after=0):
@@ -1178,15 +1122,14 @@ def uid_matrix_intersect(engine, packs, shared, after=0):
     a = _per_row(after, n, np.uint64)
     sh = np.ascontiguousarray(_np_u64(shared).ravel())
     cap = sum(min(int(p[4]), sh.size) for p in packs)
-    out_vals = np.empty(max(cap, 1), dtype=np.uint64)
-    offs = np.empty(n + 1, dtype=np.uint64)
+    out_vals, offs = _rows_out(n, cap)
     total = _u64()
     check(lib().ua_rows_intersect_packed(engine._ctx, ptrs, n, _hptr(a),
                                          _hptr(sh), sh.size,
                                          _hptr(out_vals), cap, _hptr(offs),
                                          C.byref(total)))
     del keep
-    return [out_vals[int(offs[r]):int(offs[r + 1])] for r in range(n)]
+    return _split_rows(out_vals, offs)
 
 
 def update_dest_uids(engine, rows, dest):

@@ -32,6 +32,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <iterator>
 #include <mutex>
 #include <vector>
 
@@ -5205,126 +5207,190 @@ extern "C" int ua_decode_dev(ua_ctx *c, const ua_dpack *pk, uint64_t seek_uid, u
     return run_packed_locked(c, pk, seek_uid, nullptr, 0, out, out_n, 1);
 }
 
+/* ---- one host path for the pack fan-out -> CSR matrix calls ----
+ * ua_rows_decode_dev, ua_rows_intersect_packed_dev and ua_rows_decode_mut_dev
+ * share one view of a call, ua_drowpacks itself: the block arena, the row
+ * boundaries, after, first and the two outputs.  The other two descriptors are
+ * those slots plus their own, and their entries build the view from them.
+ * Each entry reads: check, lock, reserve, count kernels, offsets, write
+ * kernels, finish.  The kernels, the event brackets and whatever differs
+ * between the calls stay in the entries. */
+#define UA_RD_MAX_BLOCKS (((u64)1 << 24) - 1) /* x 256 uids < 2^32: counts fit the u32 scan */
+
+enum { RV_VALS = 1, RV_OFFS = 2, RV_BOTH = 3 }; /* the outputs an input must not overlap */
+struct UaRowsIn {
+    const void *p;
+    size_t bytes;
+    int vs;
+};
+
+/* Everything that is rejected before c is read or locked; writes nothing.
+ * arena_vs is what the pack arrays, after and first are tested against;
+ * row_block_base is always tested against both outputs, a call's own inputs as
+ * `extras` says.  The blob's length lives on the device: deltas is held to its
+ * first byte. */
+static bool rows_args_ok(const ua_ctx *c, const ua_drowpacks &v, const uint64_t *out_total,
+                         int arena_vs, std::initializer_list<UaRowsIn> extras) {
+    if (!c || !out_total || !v.out_row_offs) return false;
+    const u64 nb = v.n_blocks, n_rows = v.n_rows;
+    if (nb && (!v.bases || !v.num_uids || !v.delta_offs || !v.deltas)) return false;
+    if (n_rows && !v.row_block_base) return false;
+    if (v.cap_vals && !v.out_vals) return false;
+    if (n_rows == 0 && nb != 0) return false;
+    /* the row grids are u32 block counts */
+    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31)) return false;
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64), ov_bytes = v.cap_vals * sizeof(u64);
+    if (ranges_overlap(v.out_vals, ov_bytes, v.out_row_offs, ro_bytes)) return false;
+    const UaRowsIn arena[] = {{v.bases, nb * sizeof(u64), arena_vs},
+                              {v.num_uids, nb * sizeof(u32), arena_vs},
+                              {v.delta_offs, nb ? (nb + 1) * sizeof(u64) : 0, arena_vs},
+                              {v.deltas, (size_t)(nb ? 1 : 0), arena_vs},
+                              {v.row_block_base, ro_bytes, RV_BOTH},
+                              {v.after, n_rows * sizeof(u64), arena_vs},
+                              {v.first, n_rows * sizeof(int32_t), arena_vs}};
+    auto clear = [&](const UaRowsIn &in) {
+        return !in.p ||
+               !(((in.vs & RV_VALS) && ranges_overlap(v.out_vals, ov_bytes, in.p, in.bytes)) ||
+                 ((in.vs & RV_OFFS) && ranges_overlap(v.out_row_offs, ro_bytes, in.p, in.bytes)));
+    };
+    return std::all_of(std::begin(arena), std::end(arena), clear) &&
+           std::all_of(extras.begin(), extras.end(), clear);
+}
+
+/* every row is empty: no launch, nothing indexes an empty array */
+static int rows_publish_empty(ua_ctx *c, const ua_drowpacks &v, uint64_t *out_total) {
+    HIP_TRY(hipMemsetAsync(v.out_row_offs, 0, (v.n_rows + 1) * sizeof(u64), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->bytes_algo += 8 * (v.n_rows + 1);
+    *out_total = 0;
+    return UA_OK;
+}
+
+/* one call's scan workspace: a count and an offset per item (a block, or in
+ * the mutation call a block or a row head), and first's window lengths per row */
+struct UaRowsWs {
+    u32 *cnt = nullptr;        /* WS_TCNT [n_items + 1] */
+    u64 *offs = nullptr;       /* WS_TOFF [n_items + 1] */
+    const u64 *part = nullptr; /* WS_PARTIAL, from rows_offsets on */
+    u32 *kcnt = nullptr;       /* WS_KLEN, all three null without first */
+    u64 *offs2 = nullptr, *part2 = nullptr;
+};
+
+static int rows_reserve_counts(ua_ctx *c, u64 n_items, UaRowsWs &w) {
+    int rc;
+    if ((rc = ws_reserve(c, WS_TCNT, (n_items + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (n_items + 1) * sizeof(u64)))) return rc;
+    w.cnt = (u32 *)c->ws[WS_TCNT];
+    w.offs = (u64 *)c->ws[WS_TOFF];
+    return UA_OK;
+}
+
+static int rows_reserve_window(ua_ctx *c, const ua_drowpacks &v, UaRowsWs &w) {
+    if (!v.first) return UA_OK;
+    const size_t kcnt_bytes = align16((v.n_rows + 1) * sizeof(u32));
+    const size_t offs2_bytes = align16((v.n_rows + 1) * sizeof(u64));
+    int rc = ws_reserve(c, WS_KLEN, kcnt_bytes + offs2_bytes +
+                                        (scan_chunks(v.n_rows + 1) + 1) * sizeof(u64));
+    if (rc) return rc;
+    w.kcnt = (u32 *)c->ws[WS_KLEN];
+    w.offs2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes);
+    w.part2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes + offs2_bytes);
+    return UA_OK;
+}
+
+/* counts -> out_row_offs: the scan over the items, the rows' offsets from it
+ * and, with first, the scan of the window lengths over them.  rbb is the rows'
+ * boundaries in items.  Adds its launches to *launches. */
+static int rows_offsets(ua_ctx *c, const ua_drowpacks &v, const u64 *rbb, u64 n_items,
+                        UaRowsWs &w, u64 *launches) {
+    int rc;
+    const u32 rgrid = (u32)(v.n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+    if ((rc = ws_scan(c, w.cnt, n_items + 1, w.offs))) return rc;
+    w.part = (const u64 *)c->ws[WS_PARTIAL];
+    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, rbb, v.n_rows,
+                       n_items, w.offs, w.part, v.first, w.kcnt, v.out_row_offs);
+    *launches += 3;
+    if (v.first) {
+        enqueue_scan(w.kcnt, v.n_rows + 1, w.offs2, w.part2, scan_chunks(v.n_rows + 1),
+                     c->stream);
+        hipLaunchKernelGGL(k_rowdec_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, w.offs2,
+                           w.part2, v.n_rows, v.out_row_offs);
+        *launches += 3;
+    }
+    return UA_OK;
+}
+
+/* The one sync of a call.  out_row_offs[n_rows] is the published total; with
+ * blocks, the blob length rides along for the byte count and the validation
+ * flag is read.  in_bytes is the call's input apart from the blob. */
+static int rows_finish(ua_ctx *c, const ua_drowpacks &v, u64 launches, u64 in_bytes,
+                       uint64_t *out_total) {
+    const bool count_only = (v.out_vals == nullptr);
+    int rc;
+    u64 total = 0, dbytes = 0;
+    HIP_TRY(hipMemcpyAsync(&total, v.out_row_offs + v.n_rows, sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    if (v.n_blocks)
+        HIP_TRY(hipMemcpyAsync(&dbytes, v.delta_offs + v.n_blocks, sizeof(u64),
+                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
+    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
+    if (v.n_blocks && (rc = pack_validate_end(c))) {
+        *out_total = 0;
+        return rc;
+    }
+    /* the call's input plus its output, not its traffic: a dropped block's
+     * deltas are never read, and a probed shared value is read more than once */
+    c->bytes_algo += dbytes + in_bytes + 8 * total;
+    *out_total = total;
+    return (!count_only && total > v.cap_vals) ? UA_ERR_INVALID : UA_OK;
+}
+
 /* ---- fan-out decode into a CSR UID matrix ----
  * handleUidPostings' per-key pl.Uids(opts) loop with opts.Intersect == nil
  * (worker/task.go:834-971, posting/list.go:1786-1902) as one call: count ->
  * scan -> (window lengths -> scan ->) write, one sync, three u64 and the
  * validation flag back to the host.  The argument checks come before c is
  * touched. */
-#define UA_RD_MAX_BLOCKS (((u64)1 << 24) - 1) /* x 256 uids < 2^32: counts fit the u32 scan */
-
 extern "C" int ua_rows_decode_dev(ua_ctx *c, const ua_drowpacks *d, uint64_t *out_total) {
-    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
-    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals;
-    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
-        return UA_ERR_INVALID;
-    if (n_rows && !d->row_block_base) return UA_ERR_INVALID;
-    if (cap && !d->out_vals) return UA_ERR_INVALID;
-    if (n_rows == 0 && nb != 0) return UA_ERR_INVALID;
-    /* the row grids are u32 block counts */
-    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31)) return UA_ERR_INVALID;
-    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
-    const size_t rbb_bytes = d->row_block_base ? ro_bytes : 0;
-    /* the blob's length lives on the device: deltas is held to its first byte */
-    const struct {
-        const void *p;
-        size_t bytes;
-    } ins[] = {{d->bases, nb * sizeof(u64)},
-               {d->num_uids, nb * sizeof(u32)},
-               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
-               {d->deltas, (size_t)(nb ? 1 : 0)},
-               {d->row_block_base, rbb_bytes},
-               {d->after, d->after ? n_rows * sizeof(u64) : 0},
-               {d->first, d->first ? n_rows * sizeof(int32_t) : 0}};
-    if (ranges_overlap(d->out_row_offs, ro_bytes, d->row_block_base, rbb_bytes) ||
-        ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
-        return UA_ERR_INVALID;
-    for (const auto &in : ins)
-        if (in.p && ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes))
-            return UA_ERR_INVALID;
-    const bool count_only = (d->out_vals == nullptr);
+    if (!d || !rows_args_ok(c, *d, out_total, RV_VALS, {})) return UA_ERR_INVALID;
+    const ua_drowpacks &v = *d;
+    const u64 nb = v.n_blocks, n_rows = v.n_rows;
 
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    if (nb == 0) { /* every row is empty: nothing indexes an empty array */
-        HIP_TRY(hipMemsetAsync(d->out_row_offs, 0, ro_bytes, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->bytes_algo += 8 * (n_rows + 1);
-        *out_total = 0;
-        return UA_OK;
-    }
+    if (nb == 0) return rows_publish_empty(c, v, out_total);
     int rc;
-    const u64 nchunks2 = scan_chunks(n_rows + 1);
-    const size_t kcnt_bytes = align16((n_rows + 1) * sizeof(u32));
-    const size_t offs2_bytes = align16((n_rows + 1) * sizeof(u64));
-    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
-    if (d->first && (rc = ws_reserve(c, WS_KLEN, kcnt_bytes + offs2_bytes +
-                                                      (nchunks2 + 1) * sizeof(u64))))
-        return rc;
-    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
-    u32 *d_kcnt = nullptr;
-    u64 *d_offs2 = nullptr, *d_part2 = nullptr;
-    if (d->first) {
-        d_kcnt = (u32 *)c->ws[WS_KLEN];
-        d_offs2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes);
-        d_part2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes + offs2_bytes);
-    }
-    HIP_TRY(hipMemsetAsync(d_cnt + nb, 0, sizeof(u32), c->stream));
-    if ((rc = pack_validate_begin(c, d->num_uids, d->delta_offs, nb))) return rc;
-    u64 launches = 1;
+    UaRowsWs w;
+    if ((rc = rows_reserve_counts(c, nb, w))) return rc;
+    if ((rc = rows_reserve_window(c, v, w))) return rc;
+    HIP_TRY(hipMemsetAsync(w.cnt + nb, 0, sizeof(u32), c->stream));
+    if ((rc = pack_validate_begin(c, v.num_uids, v.delta_offs, nb))) return rc;
+    u64 launches = 2; /* the validation and the count */
 
     const u32 nwg = (u32)((nb + UA_PKW - 1) / UA_PKW);
-    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    if (d->after)
-        hipLaunchKernelGGL(k_rowdec_count, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
-                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
-                           n_rows, d->after, d_cnt);
+    if (v.after)
+        hipLaunchKernelGGL(k_rowdec_count, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, v.bases,
+                           v.num_uids, v.delta_offs, v.deltas, nb, v.row_block_base, n_rows,
+                           v.after, w.cnt);
     else
         hipLaunchKernelGGL(k_rowdec_count_hdr, dim3((u32)((nb + UA_BLOCK - 1) / UA_BLOCK)),
-                           dim3(UA_BLOCK), 0, c->stream, d->bases, d->num_uids,
-                           d->delta_offs, nb, d_cnt);
+                           dim3(UA_BLOCK), 0, c->stream, v.bases, v.num_uids, v.delta_offs, nb,
+                           w.cnt);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if ((rc = ws_scan(c, d_cnt, nb + 1, d_offs))) return rc;
-    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
-    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
-                       d->row_block_base, n_rows, nb, d_offs, d_part, d->first, d_kcnt,
-                       d->out_row_offs);
-    launches += 4;
-    if (d->first) {
-        enqueue_scan(d_kcnt, n_rows + 1, d_offs2, d_part2, nchunks2, c->stream);
-        hipLaunchKernelGGL(k_rowdec_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d_offs2,
-                           d_part2, n_rows, d->out_row_offs);
-        launches += 3;
-    }
-    if (!count_only) {
+    if ((rc = rows_offsets(c, v, v.row_block_base, nb, w, &launches))) return rc;
+    if (v.out_vals) {
         HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-        hipLaunchKernelGGL(k_rowdec_write, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
-                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
-                           n_rows, d->after, d->first, d_cnt, d_offs, d_part,
-                           d->out_row_offs, d->out_vals, cap);
+        hipLaunchKernelGGL(k_rowdec_write, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, v.bases,
+                           v.num_uids, v.delta_offs, v.deltas, nb, v.row_block_base, n_rows,
+                           v.after, v.first, w.cnt, w.offs, w.part, v.out_row_offs, v.out_vals,
+                           v.cap_vals);
         HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     }
-    /* out_row_offs[n_rows] is the published total; the blob length rides along
-     * for the byte count */
-    u64 total = 0, dbytes = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
-    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
-    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
-    if ((rc = pack_validate_end(c))) {
-        *out_total = 0;
-        return rc;
-    }
-    c->bytes_algo += dbytes + 20 * nb + 8 * (n_rows + 1) + 8 * total;
-    *out_total = total;
-    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+    return rows_finish(c, v, launches, 20 * nb + 8 * (n_rows + 1), out_total);
 }
 
 /* ---- fan-out intersect into a CSR UID matrix ----
@@ -5336,100 +5402,49 @@ extern "C" int ua_rows_decode_dev(ua_ctx *c, const ua_drowpacks *d, uint64_t *ou
  * before c is touched. */
 extern "C" int ua_rows_intersect_packed_dev(ua_ctx *c, const ua_drowisect *d,
                                             uint64_t *out_total) {
-    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
-    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals, m = d->m;
-    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
-        return UA_ERR_INVALID;
-    if (n_rows && !d->row_block_base) return UA_ERR_INVALID;
+    if (!d) return UA_ERR_INVALID;
+    const ua_drowpacks v = {d->bases, d->num_uids, d->delta_offs, d->deltas, d->n_blocks,
+                            d->row_block_base, d->n_rows, d->after, nullptr,
+                            d->out_vals, d->cap_vals, d->out_row_offs};
+    const u64 nb = v.n_blocks, n_rows = v.n_rows, m = d->m;
     if (m && !d->shared) return UA_ERR_INVALID;
-    if (cap && !d->out_vals) return UA_ERR_INVALID;
     if (d->reserved) return UA_ERR_INVALID; /* ua_drowpacks' first: none here */
-    if (n_rows == 0 && nb != 0) return UA_ERR_INVALID;
-    /* the row grids are u32 block counts; 8 * m is a byte count below */
-    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31) || m > (UINT64_MAX >> 3))
+    if (m > (UINT64_MAX >> 3)) return UA_ERR_INVALID; /* 8 * m is a byte count below */
+    if (!rows_args_ok(c, v, out_total, RV_BOTH, {{d->shared, m * sizeof(u64), RV_BOTH}}))
         return UA_ERR_INVALID;
-    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
-    /* the blob's length lives on the device: deltas is held to its first byte */
-    const struct {
-        const void *p;
-        size_t bytes;
-    } ins[] = {{d->bases, nb * sizeof(u64)},
-               {d->num_uids, nb * sizeof(u32)},
-               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
-               {d->deltas, (size_t)(nb ? 1 : 0)},
-               {d->row_block_base, d->row_block_base ? ro_bytes : 0},
-               {d->after, d->after ? n_rows * sizeof(u64) : 0},
-               {d->shared, m * sizeof(u64)}};
-    if (ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
-        return UA_ERR_INVALID;
-    for (const auto &in : ins)
-        if (in.p && (ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes) ||
-                     ranges_overlap(d->out_row_offs, ro_bytes, in.p, in.bytes)))
-            return UA_ERR_INVALID;
-    const bool count_only = (d->out_vals == nullptr);
 
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    if (nb == 0 || m == 0) { /* every row is empty: no launch, the packs are not read */
-        HIP_TRY(hipMemsetAsync(d->out_row_offs, 0, ro_bytes, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->bytes_algo += 8 * (n_rows + 1);
-        *out_total = 0;
-        return UA_OK;
-    }
+    if (nb == 0 || m == 0) return rows_publish_empty(c, v, out_total); /* no pack is read */
     int rc;
-    if ((rc = ws_reserve(c, WS_TCNT, (nb + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TOFF, (nb + 1) * sizeof(u64)))) return rc;
-    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    UaRowsWs w;
+    if ((rc = rows_reserve_counts(c, nb, w))) return rc;
     u64 *d_keep = nullptr; /* (lo, mask) per block, count pass -> write pass */
-    if (UA_RI_KEEP && !count_only) {
+    if (UA_RI_KEEP && v.out_vals) {
         if ((rc = ws_reserve(c, WS_KLEN, nb * 2 * sizeof(u64)))) return rc;
         d_keep = (u64 *)c->ws[WS_KLEN];
     }
-    HIP_TRY(hipMemsetAsync(d_cnt + nb, 0, sizeof(u32), c->stream));
-    if ((rc = pack_validate_begin(c, d->num_uids, d->delta_offs, nb))) return rc;
+    HIP_TRY(hipMemsetAsync(w.cnt + nb, 0, sizeof(u32), c->stream));
+    if ((rc = pack_validate_begin(c, v.num_uids, v.delta_offs, nb))) return rc;
+    u64 launches = 2; /* the validation and the count */
 
     const u32 nwg = (u32)((nb + UA_PKW - 1) / UA_PKW);
-    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    hipLaunchKernelGGL(k_rowisect<false>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
-                       d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base, n_rows,
-                       d->after, d->shared, m, d_cnt, (const u64 *)nullptr,
+    hipLaunchKernelGGL(k_rowisect<false>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, v.bases,
+                       v.num_uids, v.delta_offs, v.deltas, nb, v.row_block_base, n_rows,
+                       v.after, d->shared, m, w.cnt, (const u64 *)nullptr,
                        (const u64 *)nullptr, (u64 *)nullptr, (u64)0, d_keep);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if ((rc = ws_scan(c, d_cnt, nb + 1, d_offs))) return rc;
-    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
-    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
-                       d->row_block_base, n_rows, nb, d_offs, d_part,
-                       (const int32_t *)nullptr, (u32 *)nullptr, d->out_row_offs);
-    if (!count_only) {
+    if ((rc = rows_offsets(c, v, v.row_block_base, nb, w, &launches))) return rc;
+    if (v.out_vals) {
         HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-        hipLaunchKernelGGL(k_rowisect<true>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, d->bases,
-                           d->num_uids, d->delta_offs, d->deltas, nb, d->row_block_base,
-                           n_rows, d->after, d->shared, m, d_cnt, (const u64 *)d_offs, d_part,
-                           d->out_vals, cap, d_keep);
+        hipLaunchKernelGGL(k_rowisect<true>, dim3(nwg), dim3(UA_BLOCK), 0, c->stream, v.bases,
+                           v.num_uids, v.delta_offs, v.deltas, nb, v.row_block_base, n_rows,
+                           v.after, d->shared, m, w.cnt, (const u64 *)w.offs, w.part,
+                           v.out_vals, v.cap_vals, d_keep);
         HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     }
-    u64 total = 0, dbytes = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
-    /* validation, count, scan (2), rows; then the write */
-    if ((rc = stats_add(c, c->ev[0], c->ev[1], 5))) return rc;
-    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
-    if ((rc = pack_validate_end(c))) {
-        *out_total = 0;
-        return rc;
-    }
-    /* the call's input plus its output, not its traffic: a dropped block's
-     * deltas are never read, and a probed shared value is read more than once */
-    c->bytes_algo += dbytes + 20 * nb + 8 * (n_rows + 1) + 8 * m + 8 * total;
-    *out_total = total;
-    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+    return rows_finish(c, v, launches, 20 * nb + 8 * (n_rows + 1) + 8 * m, out_total);
 }
 
 /* ---- fan-out decode with mutation layers into a CSR UID matrix ----
@@ -5443,68 +5458,37 @@ extern "C" int ua_rows_intersect_packed_dev(ua_ctx *c, const ua_drowisect *d,
  * is a row's window length (k_rowdec_rows' kcnt), at most the call's total
  * 256 * n_blocks + n_mut.  That must stay below UA_MUT_WAVE = 2^32 - 1. */
 extern "C" int ua_rows_decode_mut_dev(ua_ctx *c, const ua_drowmut *d, uint64_t *out_total) {
-    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
-    const u64 nb = d->n_blocks, n_rows = d->n_rows, cap = d->cap_vals, n_mut = d->n_mut;
-    if (n_mut == 0) { /* the same kernels, launches and stats as the plain call */
-        ua_drowpacks p = {d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
-                          d->row_block_base, n_rows, d->after, d->first,
-                          d->out_vals, cap, d->out_row_offs};
-        return ua_rows_decode_dev(c, &p, out_total);
-    }
-    if (!d->mut_uids || !d->mut_ops || !d->row_mut_base) return UA_ERR_INVALID;
-    if (nb && (!d->bases || !d->num_uids || !d->delta_offs || !d->deltas))
-        return UA_ERR_INVALID;
-    if (n_rows == 0 || !d->row_block_base) return UA_ERR_INVALID;
-    if (cap && !d->out_vals) return UA_ERR_INVALID;
-    /* the row grids are u32 block counts */
-    if (nb > UA_RD_MAX_BLOCKS || n_rows >= ((u64)UA_BLOCK << 31)) return UA_ERR_INVALID;
-    if (n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
+    if (!d) return UA_ERR_INVALID;
+    const ua_drowpacks v = {d->bases, d->num_uids, d->delta_offs, d->deltas, d->n_blocks,
+                            d->row_block_base, d->n_rows, d->after, d->first,
+                            d->out_vals, d->cap_vals, d->out_row_offs};
+    const u64 nb = v.n_blocks, n_rows = v.n_rows, cap = v.cap_vals, n_mut = d->n_mut;
+    /* the same checks, kernels, launches and stats as the plain call */
+    if (n_mut == 0) return ua_rows_decode_dev(c, &v, out_total);
+    if (!d->mut_uids || !d->mut_ops || !d->row_mut_base || n_rows == 0) return UA_ERR_INVALID;
     const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
-    /* the blob's length lives on the device: deltas is held to its first byte */
-    const struct {
-        const void *p;
-        size_t bytes;
-    } ins[] = {{d->bases, nb * sizeof(u64)},
-               {d->num_uids, nb * sizeof(u32)},
-               {d->delta_offs, nb ? (nb + 1) * sizeof(u64) : 0},
-               {d->deltas, (size_t)(nb ? 1 : 0)},
-               {d->after, d->after ? n_rows * sizeof(u64) : 0},
-               {d->first, d->first ? n_rows * sizeof(int32_t) : 0},
-               {d->mut_uids, n_mut * sizeof(u64)},
-               {d->mut_ops, n_mut}};
-    const void *const ro_ins[] = {d->row_block_base, d->mut_uids, d->mut_ops, d->row_mut_base};
-    const size_t ro_in_bytes[] = {ro_bytes, n_mut * sizeof(u64), n_mut, ro_bytes};
-    if (ranges_overlap(d->out_vals, cap * sizeof(u64), d->out_row_offs, ro_bytes))
+    if (!rows_args_ok(c, v, out_total, RV_VALS,
+                      {{d->mut_uids, n_mut * sizeof(u64), RV_BOTH},
+                       {d->mut_ops, n_mut, RV_BOTH},
+                       {d->row_mut_base, ro_bytes, RV_BOTH}}))
         return UA_ERR_INVALID;
-    for (int i = 0; i < 4; i++)
-        if (ranges_overlap(d->out_row_offs, ro_bytes, ro_ins[i], ro_in_bytes[i]) ||
-            ranges_overlap(d->out_vals, cap * sizeof(u64), ro_ins[i], ro_in_bytes[i]))
-            return UA_ERR_INVALID;
-    for (const auto &in : ins)
-        if (in.p && ranges_overlap(d->out_vals, cap * sizeof(u64), in.p, in.bytes))
-            return UA_ERR_INVALID;
-    const bool count_only = (d->out_vals == nullptr);
+    if (n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
 
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     const u64 n_items = nb + n_rows;
-    const u64 nchunks2 = scan_chunks(n_rows + 1), nchunksm = scan_chunks(n_mut + 1);
-    const size_t kcnt_bytes = align16((n_rows + 1) * sizeof(u32));
-    const size_t offs2_bytes = align16((n_rows + 1) * sizeof(u64));
+    const u64 nchunksm = scan_chunks(n_mut + 1);
     const size_t flag_bytes = align16((n_mut + 1) * sizeof(u32));
     const size_t poffs_bytes = align16((n_mut + 1) * sizeof(u64));
     const size_t ppart_bytes = align16((nchunksm + 1) * sizeof(u64));
-    if ((rc = ws_reserve(c, WS_TCNT, (n_items + 1) * sizeof(u32)))) return rc;
-    if ((rc = ws_reserve(c, WS_TOFF, (n_items + 1) * sizeof(u64)))) return rc;
+    UaRowsWs w;
+    if ((rc = rows_reserve_counts(c, n_items, w))) return rc;
     if ((rc = ws_reserve(c, WS_MUT, flag_bytes + poffs_bytes + ppart_bytes + align16(ro_bytes) +
                                         nb * sizeof(u64) + (2 * nb + 4) * sizeof(u32))))
         return rc;
-    if (d->first && (rc = ws_reserve(c, WS_KLEN, kcnt_bytes + offs2_bytes +
-                                                      (nchunks2 + 1) * sizeof(u64))))
-        return rc;
-    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
-    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    if ((rc = rows_reserve_window(c, v, w))) return rc;
+    u32 *d_cnt = w.cnt;
     u32 *d_flag = (u32 *)c->ws[WS_MUT];
     u64 *d_poffs = (u64 *)((u8 *)c->ws[WS_MUT] + flag_bytes);
     u64 *d_ppart = (u64 *)((u8 *)d_poffs + poffs_bytes);
@@ -5512,13 +5496,6 @@ extern "C" int ua_rows_decode_mut_dev(ua_ctx *c, const ua_drowmut *d, uint64_t *
     u64 *d_brow = (u64 *)((u8 *)d_ribb + align16(ro_bytes)); /* [nb] */
     u32 *d_listn = (u32 *)(d_brow + nb);                     /* [4]: two used */
     u32 *d_wlist = d_listn + 4, *d_olist = d_wlist + nb;     /* [nb] each */
-    u32 *d_kcnt = nullptr;
-    u64 *d_offs2 = nullptr, *d_part2 = nullptr;
-    if (d->first) {
-        d_kcnt = (u32 *)c->ws[WS_KLEN];
-        d_offs2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes);
-        d_part2 = (u64 *)((u8 *)c->ws[WS_KLEN] + kcnt_bytes + offs2_bytes);
-    }
     /* every item's count starts at 0: a malformed row_block_base leaves some unwritten */
     HIP_TRY(hipMemsetAsync(d_cnt, 0, (n_items + 1) * sizeof(u32), c->stream));
     HIP_TRY(hipMemsetAsync(d_listn, 0, 4 * sizeof(u32), c->stream));
@@ -5553,60 +5530,32 @@ extern "C" int ua_rows_decode_mut_dev(ua_ctx *c, const ua_drowmut *d, uint64_t *
         launches += 2;
     }
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    if ((rc = ws_scan(c, d_cnt, n_items + 1, d_offs))) return rc;
-    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
-    hipLaunchKernelGGL(k_rowdec_rows, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
-                       (const u64 *)d_ribb, n_rows, n_items, d_offs, d_part, d->first, d_kcnt,
-                       d->out_row_offs);
-    launches += 3;
-    if (d->first) {
-        enqueue_scan(d_kcnt, n_rows + 1, d_offs2, d_part2, nchunks2, c->stream);
-        hipLaunchKernelGGL(k_rowdec_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d_offs2,
-                           d_part2, n_rows, d->out_row_offs);
-        launches += 3;
-    }
-    if (!count_only) {
+    if ((rc = rows_offsets(c, v, d_ribb, n_items, w, &launches))) return rc;
+    const u64 *d_offs = w.offs, *d_part = w.part;
+    if (v.out_vals) {
         HIP_TRY(hipEventRecord(c->ev[2], c->stream));
         if (nb) {
             hipLaunchKernelGGL(k_rowmut_plain_write, dim3(nwg), dim3(UA_BLOCK), 0, c->stream,
                                d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
                                d->row_block_base, n_rows, d->after, d->first, M,
                                (const u64 *)d_brow, (const u64 *)d_ribb, (const u32 *)d_cnt,
-                               (const u64 *)d_offs, d_part, (const u64 *)d->out_row_offs,
-                               d->out_vals, cap);
+                               d_offs, d_part, (const u64 *)d->out_row_offs, d->out_vals, cap);
             hipLaunchKernelGGL(k_rowmut<true>, dim3(lgrid), dim3(UA_BLOCK), 0, c->stream,
                                d->bases, d->num_uids, d->delta_offs, d->deltas, nb,
                                d->row_block_base, n_rows, d->after, d->first, M,
                                (const u64 *)d_brow, (const u32 *)d_olist,
-                               (const u32 *)(d_listn + 1), (const u64 *)d_ribb, d_cnt,
-                               (const u64 *)d_offs, d_part, (const u64 *)d->out_row_offs,
-                               d->out_vals, cap);
+                               (const u32 *)(d_listn + 1), (const u64 *)d_ribb, d_cnt, d_offs,
+                               d_part, (const u64 *)d->out_row_offs, d->out_vals, cap);
             launches += 2;
         }
         hipLaunchKernelGGL(k_rowmut_head_write, dim3(hgrid), dim3(UA_BLOCK), 0, c->stream,
                            d->row_block_base, n_rows, nb, d->after, d->first, M,
-                           (const u64 *)d_ribb, (const u32 *)d_cnt, (const u64 *)d_offs, d_part,
+                           (const u64 *)d_ribb, (const u32 *)d_cnt, d_offs, d_part,
                            (const u64 *)d->out_row_offs, d->out_vals, cap);
         HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     }
-    u64 total = 0, dbytes = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d->out_row_offs + n_rows, sizeof(u64),
-                           hipMemcpyDeviceToHost, c->stream));
-    if (nb)
-        HIP_TRY(hipMemcpyAsync(&dbytes, d->delta_offs + nb, sizeof(u64), hipMemcpyDeviceToHost,
-                               c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipGetLastError());
-    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
-    if (!count_only && (rc = stats_add(c, c->ev[2], c->ev[3]))) return rc;
-    if (nb && (rc = pack_validate_end(c))) {
-        *out_total = 0;
-        return rc;
-    }
     /* the call's input plus its output, as for the plain call */
-    c->bytes_algo += dbytes + 20 * nb + 16 * (n_rows + 1) + 9 * n_mut + 8 * total;
-    *out_total = total;
-    return (!count_only && total > cap) ? UA_ERR_INVALID : UA_OK;
+    return rows_finish(c, v, launches, 20 * nb + 16 * (n_rows + 1) + 9 * n_mut, out_total);
 }
 
 /* ---- prepared pack fan-out (standing query plan) ---- */
@@ -6342,17 +6291,20 @@ extern "C" int ua_rows_union(ua_ctx *c, const uint64_t *vals, uint64_t total, ui
     return UA_OK;
 }
 
-/* host-pointer form of ua_rows_decode_dev: the UidMatrix of a per-key fan-out
- * (worker/task.go:834-971, one pl.Uids(opts) per key with opts.Intersect ==
- * nil) from host packs.  Flatten, upload, one device call, download; a null
- * packs[r] is an empty row. */
-extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n_rows,
-                              const uint64_t *after, const int32_t *first,
-                              uint64_t *out_vals, uint64_t cap_vals, uint64_t *out_row_offs,
-                              uint64_t *out_total) {
-    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
-    if (n_rows && !packs) return UA_ERR_INVALID;
-    if (cap_vals && !out_vals) return UA_ERR_INVALID;
+/* ---- host-pointer forms of the pack fan-out -> CSR matrix calls ----
+ * Flatten, upload, one device call, download.  The three forms share the
+ * three helpers below and keep their own null checks, their extra inputs,
+ * their descriptor and the device call. */
+struct UaHostArena { /* packs[0..n_rows) as one block arena, a null pack an empty row */
+    std::vector<u64> bases, doffs, rbb;
+    std::vector<u32> nums;
+    std::vector<u8> blob;
+    u64 nb = 0;
+};
+
+/* n_mut is the mutation call's (0 elsewhere): both limits on the block count
+ * reject before anything is allocated */
+static int rows_flatten(const ua_pack *const *packs, u64 n_rows, u64 n_mut, UaHostArena &a) {
     u64 nb = 0, db = 0;
     for (u64 r = 0; r < n_rows; r++) {
         if (!packs[r]) continue;
@@ -6362,74 +6314,125 @@ extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n
         nb += pnb;
         db += pdb;
     }
-    if (nb > UA_RD_MAX_BLOCKS) return UA_ERR_INVALID;
-    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
-    std::vector<u32> nums(nb);
-    std::vector<u8> blob(db ? db : 1);
+    if (nb > UA_RD_MAX_BLOCKS || n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
+    a.nb = nb;
+    a.bases.resize(nb);
+    a.doffs.resize(nb + 1);
+    a.rbb.resize(n_rows + 1);
+    a.nums.resize(nb);
+    a.blob.resize(db ? db : 1);
     u64 b0 = 0, off0 = 0;
     for (u64 r = 0; r < n_rows; r++) {
-        rbb[r] = b0;
+        a.rbb[r] = b0;
         if (!packs[r] || packs[r]->n_blocks == 0) continue;
-        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
-                                  doffs.data() + b0, blob.data() + off0);
+        int prc = ua_pack_flatten(packs[r], a.bases.data() + b0, a.nums.data() + b0,
+                                  a.doffs.data() + b0, a.blob.data() + off0);
         if (prc) return prc;
-        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
-        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
+        const u64 pnb = packs[r]->n_blocks, pdb = a.doffs[b0 + pnb];
+        for (u64 i = 0; i <= pnb; i++) a.doffs[b0 + i] += off0; /* pack-local -> arena */
         b0 += pnb;
         off0 += pdb;
     }
-    rbb[n_rows] = nb;
-    doffs[nb] = off0;
+    a.rbb[n_rows] = nb;
+    a.doffs[nb] = off0;
+    return UA_OK;
+}
+
+struct UaHostIn { /* one host array to upload */
+    const void *src;
+    size_t bytes, align; /* align: the element size */
+    void *dev;           /* out: where it went; null for a null src or no bytes */
+};
+
+static size_t rows_place(size_t &end, const UaHostIn &x) {
+    const size_t off = (end + x.align - 1) & ~(x.align - 1);
+    end = off + x.bytes;
+    return off;
+}
+
+/* WS_PACK takes the arena and the call's extra inputs, one after the other,
+ * every array at its natural alignment; WS_HOUT the values and then the
+ * offsets.  v gets the arena and the outputs as device pointers.  Nothing is
+ * synced: the device call's sync covers the uploads, so the host arrays must
+ * live past it. */
+static int rows_upload(ua_ctx *c, const UaHostArena &a, u64 n_rows, bool want_vals,
+                       u64 cap_vals, std::initializer_list<UaHostIn *> extras,
+                       ua_drowpacks &v) {
+    const u64 nb = a.nb, nro = n_rows + 1;
+    UaHostIn arena[] = {{a.bases.data(), nb * 8, 8, nullptr},
+                        {a.doffs.data(), (nb + 1) * 8, 8, nullptr},
+                        {a.rbb.data(), nro * 8, 8, nullptr},
+                        {a.nums.data(), nb * 4, 4, nullptr},
+                        {a.blob.data(), a.blob.size(), 1, nullptr}};
+    std::vector<UaHostIn *> all;
+    for (UaHostIn &x : arena) all.push_back(&x);
+    for (UaHostIn *x : extras)
+        if (x->src && x->bytes) all.push_back(x);
+    size_t need = 0;
+    for (const UaHostIn *x : all) rows_place(need, *x);
+    int rc;
+    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
+    size_t end = 0;
+    for (UaHostIn *x : all) {
+        x->dev = (u8 *)c->ws[WS_PACK] + rows_place(end, *x);
+        if (x->bytes)
+            HIP_TRY(hipMemcpyAsync(x->dev, x->src, x->bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    u64 *d_ov = (u64 *)c->ws[WS_HOUT];
+    v = {(const u64 *)arena[0].dev, (const u32 *)arena[3].dev, (const u64 *)arena[1].dev,
+         (const u8 *)arena[4].dev, nb, (const u64 *)arena[2].dev, n_rows, nullptr, nullptr,
+         want_vals ? d_ov : nullptr, cap_vals, d_ov + cap_vals};
+    return UA_OK;
+}
+
+/* After the device call.  Short capacity: the offsets are complete and still
+ * go back; the values only after UA_OK. */
+static int rows_download(ua_ctx *c, const ua_drowpacks &v, int rc, u64 total,
+                         uint64_t *out_vals, uint64_t *out_row_offs) {
+    if (rc && !(rc == UA_ERR_INVALID && total > v.cap_vals)) return rc;
+    const u64 nv = out_vals ? std::min<u64>(total, v.cap_vals) : 0;
+    if (nv && rc == UA_OK)
+        HIP_TRY(hipMemcpyAsync(out_vals, v.out_vals, nv * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipMemcpyAsync(out_row_offs, v.out_row_offs, (v.n_rows + 1) * sizeof(u64),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+/* host-pointer form of ua_rows_decode_dev: the UidMatrix of a per-key fan-out
+ * (worker/task.go:834-971, one pl.Uids(opts) per key with opts.Intersect ==
+ * nil) from host packs; a null packs[r] is an empty row. */
+extern "C" int ua_rows_decode(ua_ctx *c, const ua_pack *const *packs, uint64_t n_rows,
+                              const uint64_t *after, const int32_t *first,
+                              uint64_t *out_vals, uint64_t cap_vals, uint64_t *out_row_offs,
+                              uint64_t *out_total) {
+    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
+    if (n_rows && !packs) return UA_ERR_INVALID;
+    if (cap_vals && !out_vals) return UA_ERR_INVALID;
+    UaHostArena a;
+    int rc;
+    if ((rc = rows_flatten(packs, n_rows, 0, a))) return rc;
 
     std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
     HIP_TRY(hipSetDevice(c->device));
-    const u64 nro = n_rows + 1;
-    int rc;
-    size_t need = (nb + (nb + 1) + nro + n_rows) * 8 + (nb + n_rows) * 4 + blob.size();
-    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
-    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
-    u64 *d_bases = (u64 *)c->ws[WS_PACK];
-    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_after = d_rbb + nro;
-    u32 *d_nums = (u32 *)(d_after + n_rows);
-    int32_t *d_first = (int32_t *)(d_nums + nb);
-    u8 *d_blob = (u8 *)(d_first + n_rows);
-    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
-    if (nb) {
-        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
-                           c->stream));
-    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-    if (after && n_rows)
-        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
-    if (first && n_rows)
-        HIP_TRY(hipMemcpyAsync(d_first, first, n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    /* the device call's sync covers the uploads: the host vectors live past it */
-    ua_drowpacks d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
-                      after ? d_after : nullptr, first ? d_first : nullptr,
-                      out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    UaHostIn h_after = {after, n_rows * 8, 8, nullptr}, h_first = {first, n_rows * 4, 4, nullptr};
+    ua_drowpacks d;
+    if ((rc = rows_upload(c, a, n_rows, out_vals != nullptr, cap_vals, {&h_after, &h_first}, d)))
+        return rc;
+    d.after = (const u64 *)h_after.dev;
+    d.first = (const int32_t *)h_first.dev;
     u64 total = 0;
     rc = ua_rows_decode_dev(c, &d, &total);
     *out_total = total;
-    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
-    /* short capacity: the offsets are complete and still go back */
-    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
-    if (nv && rc == UA_OK)
-        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
-                               c->stream));
-    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return rc;
+    return rows_download(c, d, rc, total, out_vals, out_row_offs);
 }
 
 /* host-pointer form of ua_rows_decode_mut_dev: the UidMatrix of a per-key
  * fan-out over lists with mutable layers (one pl.Uids(opts) per key through
  * List.iterate, posting/list.go:1135-1251) from host packs and host mutation
- * slices.  Flatten, upload, one device call, download; a null packs[r] is a
- * row without blocks. */
+ * slices; a null packs[r] is a row without blocks. */
 extern "C" int ua_rows_decode_mut(ua_ctx *c, const ua_pack *const *packs, uint64_t n_rows,
                                   const uint64_t *mut_uids, const uint8_t *mut_ops,
                                   const uint64_t *row_mut_base, const uint64_t *after,
@@ -6443,91 +6446,33 @@ extern "C" int ua_rows_decode_mut(ua_ctx *c, const ua_pack *const *packs, uint64
         return ua_rows_decode(c, packs, n_rows, after, first, out_vals, cap_vals,
                               out_row_offs, out_total);
     if (!mut_uids || !mut_ops || n_mut > UINT32_MAX) return UA_ERR_INVALID;
-    u64 nb = 0, db = 0;
-    for (u64 r = 0; r < n_rows; r++) {
-        if (!packs[r]) continue;
-        u64 pnb, pdb, ptu;
-        int prc = ua_pack_flat_sizes(packs[r], &pnb, &pdb, &ptu);
-        if (prc) return prc;
-        nb += pnb;
-        db += pdb;
-    }
-    if (nb > UA_RD_MAX_BLOCKS || n_mut >= (u64)UINT32_MAX - 256 * nb) return UA_ERR_INVALID;
-    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
-    std::vector<u32> nums(nb);
-    std::vector<u8> blob(db ? db : 1);
-    u64 b0 = 0, off0 = 0;
-    for (u64 r = 0; r < n_rows; r++) {
-        rbb[r] = b0;
-        if (!packs[r] || packs[r]->n_blocks == 0) continue;
-        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
-                                  doffs.data() + b0, blob.data() + off0);
-        if (prc) return prc;
-        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
-        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
-        b0 += pnb;
-        off0 += pdb;
-    }
-    rbb[n_rows] = nb;
-    doffs[nb] = off0;
+    UaHostArena a;
+    int rc;
+    if ((rc = rows_flatten(packs, n_rows, n_mut, a))) return rc;
 
     std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
     HIP_TRY(hipSetDevice(c->device));
-    const u64 nro = n_rows + 1;
-    int rc;
-    /* u64 arrays first, then u32, then bytes: every array keeps its alignment */
-    size_t need = (nb + (nb + 1) + 2 * nro + n_rows + n_mut) * 8 + (nb + n_rows) * 4 +
-                  n_mut + blob.size();
-    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
-    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
-    u64 *d_bases = (u64 *)c->ws[WS_PACK];
-    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_rmb = d_rbb + nro;
-    u64 *d_after = d_rmb + nro, *d_muids = d_after + n_rows;
-    u32 *d_nums = (u32 *)(d_muids + n_mut);
-    int32_t *d_first = (int32_t *)(d_nums + nb);
-    u8 *d_mops = (u8 *)(d_first + n_rows);
-    u8 *d_blob = d_mops + n_mut;
-    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
-    if (nb) {
-        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
-                           c->stream));
-    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_rmb, row_mut_base, nro * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_muids, mut_uids, n_mut * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_mops, mut_ops, n_mut, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-    if (after)
-        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
-    if (first)
-        HIP_TRY(hipMemcpyAsync(d_first, first, n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    /* the device call's sync covers the uploads: the host vectors live past it */
-    ua_drowmut d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
-                    after ? d_after : nullptr, first ? d_first : nullptr,
-                    d_muids, d_mops, d_rmb, n_mut,
-                    out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    UaHostIn h_rmb = {row_mut_base, (n_rows + 1) * 8, 8, nullptr},
+             h_muids = {mut_uids, n_mut * 8, 8, nullptr}, h_mops = {mut_ops, n_mut, 1, nullptr},
+             h_after = {after, n_rows * 8, 8, nullptr}, h_first = {first, n_rows * 4, 4, nullptr};
+    ua_drowpacks p;
+    if ((rc = rows_upload(c, a, n_rows, out_vals != nullptr, cap_vals,
+                          {&h_rmb, &h_muids, &h_mops, &h_after, &h_first}, p)))
+        return rc;
+    ua_drowmut d = {p.bases, p.num_uids, p.delta_offs, p.deltas, p.n_blocks, p.row_block_base,
+                    n_rows, (const u64 *)h_after.dev, (const int32_t *)h_first.dev,
+                    (const u64 *)h_muids.dev, (const u8 *)h_mops.dev, (const u64 *)h_rmb.dev,
+                    n_mut, p.out_vals, cap_vals, p.out_row_offs};
     u64 total = 0;
     rc = ua_rows_decode_mut_dev(c, &d, &total);
     *out_total = total;
-    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
-    /* short capacity: the offsets are complete and still go back */
-    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
-    if (nv && rc == UA_OK)
-        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
-                               c->stream));
-    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return rc;
+    return rows_download(c, p, rc, total, out_vals, out_row_offs);
 }
 
 /* host-pointer form of ua_rows_intersect_packed_dev: the UidMatrix of a
  * per-key fan-out with opts.Intersect != nil (posting/list.go:1823-1829, one
  * algo.IntersectCompressedWith per key, all against q.UidList) from host
- * packs.  Flatten, upload, one device call, download; a null packs[r] is an
- * empty row. */
+ * packs; a null packs[r] is an empty row. */
 extern "C" int ua_rows_intersect_packed(ua_ctx *c, const ua_pack *const *packs,
                                         uint64_t n_rows, const uint64_t *after,
                                         const uint64_t *shared, uint64_t m,
@@ -6538,73 +6483,22 @@ extern "C" int ua_rows_intersect_packed(ua_ctx *c, const ua_pack *const *packs,
     if (m && !shared) return UA_ERR_INVALID;
     if (cap_vals && !out_vals) return UA_ERR_INVALID;
     if (m > (UINT64_MAX >> 3)) return UA_ERR_INVALID;
-    u64 nb = 0, db = 0;
-    for (u64 r = 0; r < n_rows; r++) {
-        if (!packs[r]) continue;
-        u64 pnb, pdb, ptu;
-        int prc = ua_pack_flat_sizes(packs[r], &pnb, &pdb, &ptu);
-        if (prc) return prc;
-        nb += pnb;
-        db += pdb;
-    }
-    if (nb > UA_RD_MAX_BLOCKS) return UA_ERR_INVALID;
-    std::vector<u64> bases(nb), doffs(nb + 1), rbb(n_rows + 1);
-    std::vector<u32> nums(nb);
-    std::vector<u8> blob(db ? db : 1);
-    u64 b0 = 0, off0 = 0;
-    for (u64 r = 0; r < n_rows; r++) {
-        rbb[r] = b0;
-        if (!packs[r] || packs[r]->n_blocks == 0) continue;
-        int prc = ua_pack_flatten(packs[r], bases.data() + b0, nums.data() + b0,
-                                  doffs.data() + b0, blob.data() + off0);
-        if (prc) return prc;
-        const u64 pnb = packs[r]->n_blocks, pdb = doffs[b0 + pnb];
-        for (u64 i = 0; i <= pnb; i++) doffs[b0 + i] += off0; /* pack-local -> arena */
-        b0 += pnb;
-        off0 += pdb;
-    }
-    rbb[n_rows] = nb;
-    doffs[nb] = off0;
+    UaHostArena a;
+    int rc;
+    if ((rc = rows_flatten(packs, n_rows, 0, a))) return rc;
 
     std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_PACK/WS_HOUT reuse */
     HIP_TRY(hipSetDevice(c->device));
-    const u64 nro = n_rows + 1;
-    int rc;
-    size_t need = (nb + (nb + 1) + nro + n_rows + m) * 8 + nb * 4 + blob.size();
-    if ((rc = ws_reserve(c, WS_PACK, need))) return rc;
-    if ((rc = ws_reserve(c, WS_HOUT, (cap_vals + nro) * sizeof(u64)))) return rc;
-    u64 *d_bases = (u64 *)c->ws[WS_PACK];
-    u64 *d_doffs = d_bases + nb, *d_rbb = d_doffs + nb + 1, *d_after = d_rbb + nro;
-    u64 *d_shared = d_after + n_rows;
-    u32 *d_nums = (u32 *)(d_shared + m);
-    u8 *d_blob = (u8 *)(d_nums + nb);
-    u64 *d_ov = (u64 *)c->ws[WS_HOUT], *d_oro = d_ov + cap_vals;
-    if (nb) {
-        HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_nums, nums.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(d_doffs, doffs.data(), (nb + 1) * 8, hipMemcpyHostToDevice,
-                           c->stream));
-    HIP_TRY(hipMemcpyAsync(d_rbb, rbb.data(), nro * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-    if (after && n_rows)
-        HIP_TRY(hipMemcpyAsync(d_after, after, n_rows * 8, hipMemcpyHostToDevice, c->stream));
-    if (m) HIP_TRY(hipMemcpyAsync(d_shared, shared, m * 8, hipMemcpyHostToDevice, c->stream));
-    /* the device call's sync covers the uploads: the host vectors live past it */
-    ua_drowisect d = {d_bases, d_nums, d_doffs, d_blob, nb, d_rbb, n_rows,
-                      after ? d_after : nullptr, nullptr, m ? d_shared : nullptr, m,
-                      out_vals ? d_ov : nullptr, cap_vals, d_oro};
+    UaHostIn h_after = {after, n_rows * 8, 8, nullptr}, h_shared = {shared, m * 8, 8, nullptr};
+    ua_drowpacks p;
+    if ((rc = rows_upload(c, a, n_rows, out_vals != nullptr, cap_vals, {&h_after, &h_shared}, p)))
+        return rc;
+    ua_drowisect d = {p.bases, p.num_uids, p.delta_offs, p.deltas, p.n_blocks,
+                      p.row_block_base, n_rows, (const u64 *)h_after.dev, nullptr,
+                      (const u64 *)h_shared.dev, m, p.out_vals, cap_vals, p.out_row_offs};
     u64 total = 0;
     rc = ua_rows_intersect_packed_dev(c, &d, &total);
     *out_total = total;
-    if (rc && !(rc == UA_ERR_INVALID && total > cap_vals)) return rc;
-    /* short capacity: the offsets are complete and still go back */
-    const u64 nv = out_vals ? std::min(total, cap_vals) : 0;
-    if (nv && rc == UA_OK)
-        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nv * sizeof(u64), hipMemcpyDeviceToHost,
-                               c->stream));
-    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return rc;
+    return rows_download(c, p, rc, total, out_vals, out_row_offs);
 }
+
