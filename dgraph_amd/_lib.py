@@ -123,6 +123,30 @@ class UaDRowEnc(C.Structure):
     ]
 
 
+UA_SORT_DESC = 1
+UA_SORT_MULTI = 2
+UA_SORT_DROP_NULLS = 4
+
+
+class UaDRowSort(C.Structure):
+    _fields_ = [
+        ("vals", C.c_void_p),
+        ("row_offs", C.c_void_p),
+        ("n_rows", _u64),
+        ("total", _u64),
+        ("keys", C.c_void_p),
+        ("has", C.c_void_p),
+        ("flags", _u64),
+        ("count", C.c_int32),
+        ("offset", C.c_int32),
+        ("out_vals", C.c_void_p),
+        ("cap_vals", _u64),
+        ("out_row_offs", C.c_void_p),
+        ("out_src", C.c_void_p),
+        ("out_ms_offs", C.c_void_p),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -218,6 +242,11 @@ def lib():
             L.ua_rows_encode.argtypes = [
                 C.c_void_p, _u64p, _u64p, _u64, _u64, _u64p, _u32p, _u64p, _u64, _u8p, _u64,
                 _u64p, _u64p, _u64p]
+        if L.ua_version() >= 19:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_rows_sort_dev.argtypes = [C.c_void_p, C.POINTER(UaDRowSort), _u64p]
+            L.ua_rows_sort.argtypes = [
+                C.c_void_p, _u64p, _u64p, _u64, _u64p, _u8p, _u64, C.c_int32, C.c_int32,
+                _u64p, _u64, _u64p, _u64p, C.POINTER(C.c_int32), _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

@@ -282,6 +282,95 @@ class Engine:
                                       C.c_void_p(out.data_ptr()), C.byref(n)))
         return out[:n.value]
 
+    def sort_rows(self, vals, row_offs, keys=None, has=None, count=0, offset=0, desc=False,
+                  multi=False, drop_nulls=False, count_only=False, want_src=False,
+                  out_vals=None, out_row_offs=None):
+        """Order and pagination of every row of a CSR UID matrix in ONE call
+        (ua_rows_sort_dev): sortWithoutIndex (worker/sort.go:139-187),
+        sortAndPaginateUsingVar (query/query.go:2697-2738, drop_nulls) and,
+        with keys=None, applyPagination (query/query.go:2493-2507).  vals,
+        row_offs and keys (parallel to vals, order-preserving u64) are CUDA
+        int64 tensors holding u64 bits; has is a CUDA uint8/bool tensor
+        (nonzero = the element has a key) or None.  Per row: valued elements
+        by key (ties by input position), then the nulls, then
+        x.PageRange(count, offset), grown over equal keys with multi.
+        Returns (out_vals[:total], out_row_offs[, out_src][, ms_offs]):
+        out_src (want_src) is each output element's flat input index, ms_offs
+        (multi) the int32 multiSortOffsets.  With count_only out_vals is
+        empty.  The default capacity is vals.numel(); the outputs must not
+        alias the inputs."""
+        import torch
+        from dgraph_amd._lib import (UA_SORT_DESC, UA_SORT_DROP_NULLS, UA_SORT_MULTI,
+                                     UaDRowSort)
+        dev = vals.device
+        total = vals.numel()
+        n_rows = row_offs.numel() - 1
+        if n_rows < 0:
+            raise ValueError("row_offs needs n_rows + 1 entries")
+        if keys is not None and keys.numel() != total:
+            raise ValueError("keys must be parallel to vals")
+        if has is not None:
+            if has.numel() != total:
+                raise ValueError("has must be parallel to vals")
+            if has.dtype == torch.bool:
+                has = has.view(torch.uint8)
+            if has.dtype != torch.uint8:
+                raise ValueError("has must be a uint8 or bool tensor")
+        if want_src and count_only:
+            raise ValueError("count_only delivers no out_src")
+        if out_row_offs is None:
+            out_row_offs = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        if out_row_offs.numel() < n_rows + 1:
+            raise ValueError(f"out_row_offs capacity {out_row_offs.numel()} < "
+                             f"required {n_rows + 1}")
+        cap = 0
+        if not count_only:
+            if out_vals is None:
+                out_vals = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+            cap = out_vals.numel()
+        out_src = torch.empty(max(cap, 1), dtype=torch.int64, device=dev) if want_src else None
+        ms = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev) if multi else None
+        if total == 0:  # an empty tensor has no address; "keys given" needs one
+            spare = torch.zeros(1, dtype=torch.int64, device=dev)
+            keys = spare if keys is not None else None
+            has = spare if has is not None else None
+        d = UaDRowSort()
+        d.vals = vals.data_ptr()
+        d.row_offs = row_offs.data_ptr()
+        d.n_rows = n_rows
+        d.total = total
+        d.keys = keys.data_ptr() if keys is not None else None
+        d.has = has.data_ptr() if has is not None else None
+        d.flags = ((UA_SORT_DESC if desc else 0) | (UA_SORT_MULTI if multi else 0) |
+                   (UA_SORT_DROP_NULLS if drop_nulls else 0))
+        d.count = int(count)
+        d.offset = int(offset)
+        d.out_vals = None if count_only else out_vals.data_ptr()
+        d.cap_vals = cap
+        d.out_row_offs = out_row_offs.data_ptr()
+        d.out_src = out_src.data_ptr() if want_src else None
+        d.out_ms_offs = ms.data_ptr() if multi else None
+        need = _u64()
+        rc = lib().ua_rows_sort_dev(self._ctx, C.byref(d), C.byref(need))
+        if rc == 3 and not count_only and need.value > cap:
+            raise ValueError(f"out_vals capacity {cap} < required {need.value}")
+        check(rc)
+        if count_only:
+            res = [torch.empty(0, dtype=torch.int64, device=dev), out_row_offs[:n_rows + 1]]
+        else:
+            res = [out_vals[:need.value], out_row_offs[:n_rows + 1]]
+        if want_src:
+            res.append(out_src[:need.value])
+        if multi:
+            res.append(ms[:n_rows])
+        return tuple(res)
+
+    def paginate_rows(self, vals, row_offs, count, offset):
+        """applyPagination (query/query.go:2493-2507) and the cascade
+        paginations (query/query.go:1483-1487, 3006-3010): x.PageRange(count,
+        offset) of every row as one call — sort_rows with keys=None."""
+        return self.sort_rows(vals, row_offs, count=count, offset=offset)
+
     # ---- packed (codec) path ----
     def upload_pack(self, bases, num_uids, delta_offs, deltas_blob, block_size):
         """Upload flat pack arrays (from encode_flat) -> DPack on this GPU."""
@@ -1099,6 +1188,56 @@ def encode_rows(engine, rows, block_size=256):
         out.append((bases[b0:b1], nums[b0:b1], doffs[b0:b1 + 1] - np.uint64(y0),
                     blob[y0:y1], int(rows[r].size)))
     return out
+
+
+def sort_uid_matrix(engine, rows, keys, count=0, offset=0, desc=False, multi=False,
+                    drop_nulls=False, want_src=False):
+    """sortWithoutIndex (worker/sort.go:139-187) or, with drop_nulls,
+    sortAndPaginateUsingVar (query/query.go:2697-2738) over a whole UID matrix
+    as ONE call (ua_rows_sort).  rows: sequences of uids; keys: one parallel
+    sequence per row of order-preserving u64 keys, a None entry meaning the
+    uid has no value.  Returns (rows, ms_offs): the ordered, paginated rows and
+    the multiSortOffsets ([] unless multi); with want_src also each row's flat
+    input indices, as a third item."""
+    from dgraph_amd._lib import UA_SORT_DESC, UA_SORT_DROP_NULLS, UA_SORT_MULTI
+    n = len(rows)
+    rows = [_np_u64(r).ravel() for r in rows]
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([r.size for r in rows], dtype=np.uint64)
+    total = int(offs[n])
+    vals = np.ascontiguousarray(np.concatenate(rows)) if n else np.empty(0, np.uint64)
+    kk = has = None
+    if keys is not None:
+        if len(keys) != n or any(len(k) != r.size for k, r in zip(keys, rows)):
+            raise ValueError("keys must be parallel to rows")
+        flat = [x for k in keys for x in k]
+        has = np.array([x is not None for x in flat], dtype=np.uint8)
+        kk = np.array([0 if x is None else int(x) for x in flat], dtype=np.uint64)
+    flags = ((UA_SORT_DESC if desc else 0) | (UA_SORT_MULTI if multi else 0) |
+             (UA_SORT_DROP_NULLS if drop_nulls else 0))
+    out = np.empty(max(total, 1), dtype=np.uint64)
+    src = np.empty(max(total, 1), dtype=np.uint64) if want_src else None
+    ooffs = np.empty(n + 1, dtype=np.uint64)
+    ms = np.zeros(max(n, 1), dtype=np.int32) if multi else None
+    need = _u64()
+    check(lib().ua_rows_sort(
+        engine._ctx, _hptr(vals), _hptr(offs), n,
+        _hptr(kk) if kk is not None else None,
+        (has if has.size else np.zeros(1, np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8))
+        if has is not None else None,
+        flags, int(count), int(offset), _hptr(out), total, _hptr(ooffs),
+        _hptr(src) if want_src else None,
+        ms.ctypes.data_as(C.POINTER(C.c_int32)) if multi else None, C.byref(need)))
+    res = (_split_rows(out, ooffs), [int(x) for x in ms[:n]] if multi else [])
+    if want_src:
+        res += (_split_rows(src, ooffs),)
+    return res
+
+
+def paginate_uid_matrix(engine, rows, count, offset):
+    """applyPagination (query/query.go:2493-2507): x.PageRange(count, offset)
+    of every row as ONE call (ua_rows_sort without keys).  Returns the rows."""
+    return sort_uid_matrix(engine, rows, None, count=count, offset=offset)[0]
 
 
 def rollup_rows(engine, packs, muts, block_size=256):

@@ -3500,6 +3500,430 @@ __global__ __launch_bounds__(UA_BLOCK) void k_rowenc_rows(
     }
 }
 
+/* ==================== kernels: sort and paginate a CSR UID matrix ====================
+ * Order and pagination of every row of a CSR matrix in one call (DESIGN.md
+ * §4.11): applyPagination (query/query.go:2493-2507), sortWithoutIndex
+ * (worker/sort.go:139-187: sortByValue :775-821, paginate :740-772),
+ * sortAndPaginateUsingVar (query/query.go:2697-2738) and the cascade
+ * paginations (query/query.go:1483-1487, 3006-3010), with x.PageRange
+ * (x/x.go:815-844) word for word.
+ *
+ * A record is (key', tag): key' = key, ~key under UA_SORT_DESC, 0 for an
+ * element without a key; tag = null << 31 | flat input index.  Inside a row
+ * records are ordered by (null, key', index), which is a total order, so every
+ * merge below is deterministic and ties keep input order in both directions.
+ * Tiles are cut over the FLAT element array; a row's segments are its
+ * intersections with the tile grid.  k_rsort_tiles sorts each tile by (row,
+ * record), which finishes every row inside one tile; round k of k_rsort_round
+ * merges a row's groups of 2^k segments pairwise, aligned to the ROW's first
+ * tile, between two record buffers.  A row of s segments is final after
+ * ceil(log2 s) rounds, so the buffer it ends in follows from s alone. */
+
+#define UA_RS_IDX 0x7fffffffu /* tag: flat input index */
+#define UA_RS_NULL 0x80000000u /* tag: the element has no key */
+static_assert(UA_RTILE == 2048 && UA_RWORDS == 32,
+              "k_rsort_tiles packs (row in tile, null, position in tile) into 11+1+11 bits");
+
+__device__ __forceinline__ bool d_rs_less(u64 kx, u32 tx, u64 ky, u32 ty) {
+    const u32 nx = tx >> 31, ny = ty >> 31;
+    if (nx != ny) return nx < ny;
+    if (kx != ky) return kx < ky;
+    return tx < ty;
+}
+
+__device__ __forceinline__ u32 d_rs_ceil_log2(u32 s) { /* s >= 1 */
+    return s <= 1 ? 0u : 32u - (u32)__clz(s - 1);
+}
+
+/* row r's clamped range [a, b) and its segment count (0 for an empty row) */
+__device__ __forceinline__ void d_rs_row(const u64 *__restrict__ row_offs, u64 r, u64 total,
+                                         u32 &a, u32 &b, u32 &nseg) {
+    u64 x = row_offs[r], y = row_offs[r + 1];
+    x = x < total ? x : total;
+    y = y < total ? y : total;
+    if (y < x) y = x;
+    a = (u32)x;
+    b = (u32)y;
+    nseg = (b > a) ? (b - 1) / UA_RTILE - a / UA_RTILE + 1 : 0;
+}
+
+/* one thread per row: a non-empty row sets the bit of its (clamped) start, as
+ * k_rowenc_rowbits does, and the largest segment count goes to *maxseg */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_rowbits(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total,
+    unsigned long long *__restrict__ rowbits, u32 *__restrict__ maxseg) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    u32 a, b, nseg;
+    d_rs_row(row_offs, r, total, a, b, nseg);
+    if (a < b) atomicOr(&rowbits[a >> 6], 1ull << (a & 63)); /* a < total */
+    /* elements past the last row belong to no row: keep them out of its sort */
+    if (r == n_rows - 1 && b < total) atomicOr(&rowbits[b >> 6], 1ull << (b & 63));
+    if (nseg > 1) atomicMax(maxseg, nseg);
+}
+
+/* One workgroup per UA_RTILE flat elements: sort the tile in LDS by (row in
+ * tile, null, key', position) and store the records at the tile's own flat
+ * positions.  The row number of an element is the count of row-start bits at
+ * or below it, so no row descriptor is read.  Padding past total carries the
+ * largest local tag and sorts last.  tile_rows[2t], [2t + 1]: the rows holding
+ * the tile's first and last element (upper bounds over row_offs; a broken
+ * row_offs gives some row, which k_rsort_round checks before it trusts it). */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_tiles(
+    const u64 *__restrict__ keys, const u8 *__restrict__ has, u64 total, u32 desc,
+    const u64 *__restrict__ rowbits, const u64 *__restrict__ row_offs, u64 n_rows,
+    u64 *__restrict__ rkey, u32 *__restrict__ rtag, u32 *__restrict__ tile_rows) {
+    __shared__ u64 s_key[UA_RTILE];
+    __shared__ u32 s_tag[UA_RTILE];
+    __shared__ u32 s_wpre[UA_RWORDS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 tile = blockIdx.x;
+    const u64 t0 = tile * UA_RTILE;
+    const int len = (int)((total - t0 < UA_RTILE) ? total - t0 : UA_RTILE); /* t0 < total */
+
+    if (wv == 0) { /* exclusive scan of the 32 words' start-bit counts; the bit
+                    * of the tile's first element does not count, so rows number
+                    * 0 .. UA_RTILE - 1 whether or not a row starts at t0 */
+        u64 w = lane < UA_RWORDS ? rowbits[tile * UA_RWORDS + lane] : 0;
+        if (lane == 0) w &= ~1ull;
+        u32 cw = (u32)__popcll(w);
+        u32 incl = cw;
+#pragma unroll
+        for (int o = 1; o < UA_RWORDS; o <<= 1) {
+            u32 x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        if (lane < UA_RWORDS) s_wpre[lane] = incl - cw;
+    } else if (wv <= 2) { /* waves 1, 2: the rows of the first and the last element */
+        u64 p = (wv == 1) ? t0 : t0 + (u64)len - 1;
+        u64 idx = d_wave_lower_bound(row_offs, n_rows + 1, p + 1, lane); /* first > p */
+        u64 r = idx ? idx - 1 : 0;
+        if (r >= n_rows) r = n_rows - 1; /* n_rows >= 1: total > 0 */
+        if (lane == 0) tile_rows[2 * tile + (wv - 1)] = (u32)r;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int i = s * UA_BLOCK + tid, q = i >> 6;
+        u64 k = 0;
+        u32 tg = 0xffffffffu;
+        if (i < len) {
+            bool hv = has ? has[t0 + i] != 0 : true;
+            k = keys[t0 + i];
+            k = hv ? (desc ? ~k : k) : 0;
+            u64 w = rowbits[tile * UA_RWORDS + q]; /* wave-uniform address */
+            if (q == 0) w &= ~1ull;
+            u32 row = s_wpre[q] + (u32)__popcll(w & ((2ull << lane) - 1)); /* < UA_RTILE */
+            tg = (row << 12) | ((hv ? 0u : 1u) << 11) | (u32)i;
+        }
+        s_key[i] = k;
+        s_tag[i] = tg;
+    }
+    __syncthreads();
+    /* the bitonic network of k_sort_chunks over (tag >> 11, key, tag) */
+    for (int k = 2; k <= UA_RTILE; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < UA_RTILE; i += UA_BLOCK) {
+                int p = i ^ j;
+                if (p > i) {
+                    bool up = ((i & k) == 0);
+                    u64 kx = s_key[i], ky = s_key[p];
+                    u32 tx = s_tag[i], ty = s_tag[p];
+                    u32 hx = tx >> 11, hy = ty >> 11;
+                    bool gt = hx != hy ? hx > hy : (kx != ky ? kx > ky : tx > ty);
+                    if (gt == up) {
+                        s_key[i] = ky;
+                        s_key[p] = kx;
+                        s_tag[i] = ty;
+                        s_tag[p] = tx;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int i = s * UA_BLOCK + tid;
+        if (i < len) { /* the len real records sort before the padding */
+            u32 tg = s_tag[i];
+            rkey[t0 + i] = s_key[i];
+            rtag[t0 + i] = (((tg >> 11) & 1u) << 31) | (u32)(t0 + (tg & (UA_RTILE - 1)));
+        }
+    }
+}
+
+/* merge-path split of diagonal d over A[0, na) and B[0, nb): the number of A
+ * records among the first d of the merge.  The order is total, so one strict
+ * comparison decides.  Every probe lies inside A or B. */
+__device__ __forceinline__ u32 d_rs_split(const u64 *__restrict__ ak, const u32 *__restrict__ at,
+                                          u32 na, const u64 *__restrict__ bk,
+                                          const u32 *__restrict__ bt, u32 nb, u32 d) {
+    u32 lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        u32 m = (lo + hi) >> 1; /* m < na, d - 1 - m < nb */
+        if (d_rs_less(ak[m], at[m], bk[d - 1 - m], bt[d - 1 - m])) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+
+/* Round k, one workgroup per flat tile: for the (at most two) rows that span
+ * several tiles and touch this tile, produce the records of the tile's own
+ * flat positions in the merge of the row's group pair, from src into dst.  A
+ * group without a partner is copied.  Rows that are final (2^k >= segments)
+ * and rows inside one tile are not touched.  Every value that decides a
+ * barrier is workgroup-uniform: it comes from blockIdx, kernel arguments and
+ * LDS words written before a barrier. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_round(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total, const u32 *__restrict__ tile_rows,
+    const u32 *__restrict__ maxseg, u32 k, const u64 *__restrict__ skey,
+    const u32 *__restrict__ stag, u64 *__restrict__ dkey, u32 *__restrict__ dtag) {
+    __shared__ u64 s_key[UA_RTILE];
+    __shared__ u32 s_tag[UA_RTILE];
+    __shared__ u32 s_sp[2];
+    const int tid = threadIdx.x;
+    if (((u64)1 << k) >= (u64)*maxseg) return; /* uniform: no row needs this round */
+    const u32 t = blockIdx.x;
+    const u32 t0 = t * UA_RTILE;
+    const u32 tend = (total - t0 < UA_RTILE) ? (u32)total : t0 + UA_RTILE;
+    u32 rows[2] = {tile_rows[2 * t], tile_rows[2 * t + 1]};
+    const int nparts = rows[0] == rows[1] ? 1 : 2;
+    for (int part = 0; part < nparts; part++) {
+        u32 r = rows[part];
+        if (r >= n_rows) continue; /* uniform */
+        u32 a, b, nseg;
+        d_rs_row(row_offs, r, total, a, b, nseg);
+        /* the row must hold the tile's first (part 0) or last (part 1) element */
+        const u32 probe = part == 0 ? t0 : tend - 1;
+        if (!(a <= probe && probe < b) || nseg < 2 || ((u64)1 << k) >= nseg) continue;
+        const u32 T0 = a / UA_RTILE, j = t - T0; /* j < nseg */
+        const u32 s0 = (j >> (k + 1)) << (k + 1), smid = s0 + (1u << k);
+        u64 s1w = (u64)s0 + ((u64)2 << k);
+        const u32 s1 = s1w < nseg ? (u32)s1w : nseg;
+        const u32 o0 = a > t0 ? a : t0, o1 = b < tend ? b : tend; /* o0 < o1 <= o0 + UA_RTILE */
+        const u32 cnt = o1 - o0;
+        if (smid >= nseg) { /* no partner: copy */
+            for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+                dkey[o0 + i] = skey[o0 + i];
+                dtag[o0 + i] = stag[o0 + i];
+            }
+            continue;
+        }
+        const u32 L0 = s0 == 0 ? a : (T0 + s0) * UA_RTILE;
+        const u32 L1 = (T0 + smid) * UA_RTILE; /* smid < nseg: inside the row */
+        const u32 R1 = s1 >= nseg ? b : (T0 + s1) * UA_RTILE;
+        const u32 na = L1 - L0, nb = R1 - L1;
+        __syncthreads(); /* the previous part's LDS reads are done */
+        if (tid < 2)
+            s_sp[tid] = d_rs_split(skey + L0, stag + L0, na, skey + L1, stag + L1, nb,
+                                   (tid == 0 ? o0 : o1) - L0);
+        __syncthreads();
+        const u32 i0 = s_sp[0], i1 = s_sp[1];
+        const u32 j0 = (o0 - L0) - i0;
+        const u32 ca = i1 - i0; /* A records; the other cnt - ca come from B at j0 */
+        for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+            u32 g = i < ca ? L0 + i0 + i : L1 + j0 + (i - ca);
+            s_key[i] = skey[g];
+            s_tag[i] = stag[g];
+        }
+        __syncthreads();
+        u64 mk[UA_RSTEPS];
+        u32 mt[UA_RSTEPS], mr[UA_RSTEPS];
+#pragma unroll
+        for (int s = 0; s < UA_RSTEPS; s++) {
+            const u32 i = (u32)s * UA_BLOCK + tid;
+            mr[s] = UA_RTILE;
+            if (i < cnt) {
+                mk[s] = s_key[i];
+                mt[s] = s_tag[i];
+                /* rank = own index in its part + records of the other part below it */
+                u32 lo, hi, own;
+                if (i < ca) { lo = ca; hi = cnt; own = i; }
+                else { lo = 0; hi = ca; own = i - ca; }
+                const u32 base = lo;
+                while (lo < hi) {
+                    u32 m = (lo + hi) >> 1;
+                    if (d_rs_less(s_key[m], s_tag[m], mk[s], mt[s])) lo = m + 1;
+                    else hi = m;
+                }
+                mr[s] = own + (lo - base);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < UA_RSTEPS; s++)
+            if (mr[s] < cnt) {
+                s_key[mr[s]] = mk[s];
+                s_tag[mr[s]] = mt[s];
+            }
+        __syncthreads();
+        for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+            dkey[o0 + i] = s_key[i];
+            dtag[o0 + i] = s_tag[i];
+        }
+    }
+}
+
+/* x.PageRange (x/x.go:815-844) */
+__device__ __forceinline__ void d_page_range(long long count, long long offset, long long n,
+                                             long long &start, long long &end) {
+    if (n == 0) { start = 0; end = 0; return; }
+    if (count == 0 && offset == 0) { start = 0; end = n; return; }
+    if (count < 0) {
+        if (-count > n) count = -n;
+        start = (((n + count) % n) + n) % n;
+        end = n;
+        return;
+    }
+    start = offset < 0 ? 0 : offset;
+    if (start > n) { start = n; end = n; return; }
+    if (count == 0) { end = n; return; }
+    end = start + count;
+    if (end > n) end = n;
+}
+
+/* One thread per row: |V| from the sorted run, PageRange over S, the
+ * UA_SORT_MULTI extension by binary search in the run's keys, then the row's
+ * output length, the page's first rank and multiSortOffsets.  sorted == 0
+ * (page only, or a count-only call whose lengths do not depend on the order)
+ * reads no record.  Thread n_rows writes the zero count that closes the scan. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_page(
+    const u64 *__restrict__ row_offs, u64 n_rows, u64 total, const u64 *__restrict__ key0,
+    const u32 *__restrict__ tag0, const u64 *__restrict__ key1, const u32 *__restrict__ tag1,
+    u32 sorted, u32 flags, int count, int offset, u32 *__restrict__ row_len,
+    u32 *__restrict__ row_start, int *__restrict__ out_ms_offs, u32 *__restrict__ bad) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    if (r == n_rows) {
+        row_len[r] = 0;
+        return;
+    }
+    u32 a, b, nseg;
+    d_rs_row(row_offs, r, total, a, b, nseg);
+    {   /* a clamped end below its start: rows may overlap, the lengths may sum
+         * past total.  The later kernels then publish empty rows. */
+        u64 y = row_offs[r + 1];
+        if ((y < total ? y : total) < a) atomicOr(bad, 1u);
+    }
+    const u32 n = b - a;
+    u32 nv = n, lenS = n;
+    const u64 *rk = nullptr;
+    if (sorted && n) {
+        const bool odd = d_rs_ceil_log2(nseg) & 1;
+        rk = (odd ? key1 : key0) + a;
+        const u32 *rt = (odd ? tag1 : tag0) + a;
+        u32 lo = 0, hi = n; /* first null of the run */
+        while (lo < hi) {
+            u32 m = (lo + hi) >> 1;
+            if (rt[m] & UA_RS_NULL) hi = m;
+            else lo = m + 1;
+        }
+        nv = lo;
+        if ((flags & UA_SORT_DROP_NULLS) && nv) lenS = nv; /* nv == 0: the row stays */
+    }
+    long long start, end;
+    d_page_range(count, offset, lenS, start, end);
+    if ((flags & UA_SORT_MULTI) && rk) {
+        if (start > 0 && start < nv) { /* first of the equal run holding S[start] */
+            const u64 kk = rk[start];
+            u32 lo = 0, hi = (u32)start;
+            while (lo < hi) {
+                u32 m = (lo + hi) >> 1;
+                if (rk[m] < kk) lo = m + 1;
+                else hi = m;
+            }
+            start = lo;
+        }
+        if (end > 0 && end < nv) { /* one past the equal run holding S[end - 1] */
+            const u64 kk = rk[end - 1];
+            u32 lo = (u32)end, hi = nv;
+            while (lo < hi) {
+                u32 m = (lo + hi) >> 1;
+                if (rk[m] <= kk) lo = m + 1;
+                else hi = m;
+            }
+            end = lo;
+        }
+    }
+    if (end < start) end = start;
+    row_len[r] = (u32)(end - start);
+    row_start[r] = (u32)start;
+    if (out_ms_offs) {
+        long long off = offset; /* sort.go:170-178 */
+        out_ms_offs[r] = start < off ? (int)(off - start) : 0;
+    }
+}
+
+/* one thread per boundary: out_row_offs from the scan over the row lengths;
+ * thread n_rows also publishes the total.  After a row_offs that descends
+ * (*bad) every row is empty: disjoint rows are what keeps the total at or
+ * below the input's. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_offs(
+    u64 n_rows, const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    const u32 *__restrict__ bad, u64 *__restrict__ out_row_offs, u64 *__restrict__ out_total) {
+    u64 r = (u64)blockIdx.x * UA_BLOCK + threadIdx.x;
+    if (r > n_rows) return;
+    u64 x = *bad ? 0 : d_off(offs, part, r);
+    out_row_offs[r] = x;
+    if (r == n_rows) *out_total = x;
+}
+
+/* last boundary <= o in the scanned lengths, searched inside [lo, hi] */
+__device__ __forceinline__ u32 d_rs_row_of(const u64 *__restrict__ offs,
+                                           const u64 *__restrict__ part, u32 lo, u32 hi,
+                                           u64 o) {
+    while (lo < hi) { /* invariant: boundary(lo) <= o */
+        u32 m = lo + (hi - lo + 1) / 2;
+        if (d_off(offs, part, m) <= o) lo = m;
+        else hi = m - 1;
+    }
+    return lo;
+}
+
+/* Flat write pass, one thread per OUTPUT element below min(total, cap_vals):
+ * the element's row is the last boundary at or below it in the scanned row
+ * lengths (monotone by construction, whatever row_offs holds); the workgroup
+ * first brackets the rows of its 256 elements, so a thread searches only
+ * those.  The source index comes from the row's run (clamped below total:
+ * with a broken row_offs a run may hold records no round wrote), or is the
+ * input position itself when the call only pages. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rsort_write(
+    const u64 *__restrict__ vals, const u64 *__restrict__ row_offs, u64 n_rows, u64 total,
+    const u32 *__restrict__ tag0, const u32 *__restrict__ tag1, u32 sorted,
+    const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    const u32 *__restrict__ row_start, const u32 *__restrict__ bad,
+    u64 *__restrict__ out_vals, u64 *__restrict__ out_src, u64 cap_vals) {
+    __shared__ u32 s_r[2];
+    const int tid = threadIdx.x;
+    if (*bad) return; /* uniform: every row was published empty */
+    const u64 out_n = d_off(offs, part, n_rows);
+    const u64 lim = out_n < cap_vals ? out_n : cap_vals;
+    const u64 o_first = (u64)blockIdx.x * UA_BLOCK;
+    if (o_first >= lim) return; /* uniform */
+    const u64 o_last = (o_first + UA_BLOCK - 1 < lim) ? o_first + UA_BLOCK - 1 : lim - 1;
+    if (tid < 2)
+        s_r[tid] = d_rs_row_of(offs, part, 0, (u32)n_rows, tid == 0 ? o_first : o_last);
+    __syncthreads();
+    const u64 o = o_first + tid;
+    if (o >= lim) return;
+    /* boundary(r) <= o < out_n = boundary(n_rows), so r < n_rows */
+    u32 r = d_rs_row_of(offs, part, s_r[0], s_r[1], o);
+    if (r >= n_rows) return;
+    u32 a, b, nseg;
+    d_rs_row(row_offs, r, total, a, b, nseg);
+    u64 p = (u64)a + row_start[r] + (o - d_off(offs, part, r)); /* < b by the page kernel */
+    if (p >= total) return;
+    u64 src = p;
+    if (sorted) {
+        const u32 *rt = (d_rs_ceil_log2(nseg) & 1) ? tag1 : tag0;
+        src = rt[p] & UA_RS_IDX;
+        if (src >= total) src = total - 1;
+    }
+    out_vals[o] = vals[src];
+    if (out_src) out_src[o] = src;
+}
+
 /* ==================== host shim ==================== */
 
 static thread_local hipError_t g_last_hip = hipSuccess;
@@ -3549,7 +3973,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 18; }
+extern "C" int ua_version(void) { return 19; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -5908,6 +6332,225 @@ extern "C" int ua_rows_encode(ua_ctx *c, const uint64_t *vals, const uint64_t *r
 }
 
 /* ==================== host-side codec (codec.Encode restated) ==================== */
+
+/* ---- sort and paginate a CSR UID matrix ----
+ * applyPagination (query/query.go:2493-2507), sortWithoutIndex
+ * (worker/sort.go:139-187), sortAndPaginateUsingVar (query/query.go:2697-2738)
+ * and the cascade paginations (query/query.go:1483-1487, 3006-3010) for every
+ * row in one call: row bits -> tile sort -> merge rounds -> page -> scan ->
+ * offsets (-> write), one sync, one u64 back to the host.  The argument checks
+ * come before c is touched. */
+static u32 rsort_rounds(u64 ntiles) { /* ceil(log2(ntiles)) */
+    u32 k = 0;
+    while (((u64)1 << k) < ntiles) k++;
+    return k;
+}
+
+extern "C" int ua_rows_sort_dev(ua_ctx *c, const ua_drowsort *d, uint64_t *out_total) {
+    if (!c || !d || !out_total || !d->out_row_offs) return UA_ERR_INVALID;
+    const u64 total = d->total, n_rows = d->n_rows, flags = d->flags;
+    if (total && !d->vals) return UA_ERR_INVALID;
+    if (n_rows && !d->row_offs) return UA_ERR_INVALID;
+    if (n_rows == 0 && total != 0) return UA_ERR_INVALID;
+    if (!d->keys && (flags || d->has)) return UA_ERR_INVALID;
+    if (flags & ~(u64)(UA_SORT_DESC | UA_SORT_MULTI | UA_SORT_DROP_NULLS)) return UA_ERR_INVALID;
+    if ((flags & UA_SORT_MULTI) && (flags & UA_SORT_DROP_NULLS)) return UA_ERR_INVALID;
+    if (d->out_ms_offs && !(flags & UA_SORT_MULTI)) return UA_ERR_INVALID;
+    if (d->out_src && !d->out_vals) return UA_ERR_INVALID;
+    if (!d->out_vals && d->cap_vals) return UA_ERR_INVALID;
+    /* a flat index and the null bit share a 32-bit tag */
+    if (total >= ((u64)1 << 31) || n_rows >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    if (d->cap_vals >= ((u64)1 << 60)) return UA_ERR_INVALID; /* byte sizes below stay in u64 */
+    const bool count_only = !d->out_vals;
+    const size_t ro_bytes = (n_rows + 1) * sizeof(u64);
+    const struct {
+        const void *p;
+        size_t bytes;
+    } rg[] = {{d->vals, total * sizeof(u64)},
+              {d->row_offs, d->row_offs ? ro_bytes : 0},
+              {d->keys, total * sizeof(u64)},
+              {d->has, total},
+              {d->out_row_offs, ro_bytes},
+              {d->out_vals, d->cap_vals * sizeof(u64)},
+              {d->out_src, d->cap_vals * sizeof(u64)},
+              {d->out_ms_offs, n_rows * sizeof(int32_t)}};
+    const int n_rg = (int)(sizeof(rg) / sizeof(rg[0]));
+    for (int a = 4; a < n_rg; a++) /* every output against the inputs and the other outputs */
+        for (int b = 0; b < a; b++)
+            if (rg[a].p && rg[b].p && ranges_overlap(rg[a].p, rg[a].bytes, rg[b].p, rg[b].bytes))
+                return UA_ERR_INVALID;
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 in_bytes = 8 * total + (d->keys ? 8 * total : 0) + (d->has ? total : 0) +
+                         8 * (n_rows + 1);
+    /* The lengths depend on the order only through the MULTI extension and |V|.
+     * total == 0 takes the page-only path: every row is empty, but out_ms_offs
+     * still receives max(offset, 0) per row (sort.go:170-178 with start == 0). */
+    const bool sorted = d->keys && total &&
+                        !(count_only && !(flags & (UA_SORT_MULTI | UA_SORT_DROP_NULLS)));
+    const u64 ntiles = (total + UA_RTILE - 1) / UA_RTILE;
+    const u32 rounds = sorted ? rsort_rounds(ntiles) : 0;
+    const size_t bits_bytes = (size_t)(ntiles * UA_RWORDS + 1) * sizeof(u64);
+    const size_t rs_bytes = align16(n_rows * sizeof(u32));
+    int rc;
+    if (sorted) {
+        if ((rc = ws_reserve(c, WS_SCRATCH_A, bits_bytes))) return rc;
+        if ((rc = ws_reserve(c, WS_SCRATCH_B, (size_t)total * 24))) return rc;
+        if ((rc = ws_reserve(c, WS_RKW, (size_t)ntiles * 2 * sizeof(u32)))) return rc;
+    }
+    if ((rc = ws_reserve(c, WS_TCNT, (size_t)(n_rows + 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (size_t)(n_rows + 1) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_KLEN, rs_bytes + 2 * sizeof(u64)))) return rc;
+    u64 *d_bits = (u64 *)c->ws[WS_SCRATCH_A];
+    u64 *d_key[2] = {nullptr, nullptr};
+    u32 *d_tag[2] = {nullptr, nullptr};
+    if (sorted) {
+        d_key[0] = (u64 *)c->ws[WS_SCRATCH_B];
+        d_key[1] = d_key[0] + total;
+        d_tag[0] = (u32 *)(d_key[1] + total);
+        d_tag[1] = d_tag[0] + total;
+    }
+    u32 *d_trows = (u32 *)c->ws[WS_RKW];
+    u32 *d_len = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    u32 *d_rstart = (u32 *)c->ws[WS_KLEN];
+    /* word 0: u32 max segments, u32 "row_offs descends"; word 1: the total */
+    u64 *d_words = (u64 *)((u8 *)c->ws[WS_KLEN] + rs_bytes);
+    u32 *d_bad = (u32 *)d_words + 1;
+    const u32 rgrid = (u32)(n_rows / UA_BLOCK + 1); /* n_rows + 1 threads */
+    u64 launches = 0;
+
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(hipMemsetAsync(d_words, 0, sizeof(u64), c->stream));
+    if (sorted) {
+        HIP_TRY(hipMemsetAsync(d_bits, 0, bits_bytes, c->stream));
+        hipLaunchKernelGGL(k_rsort_rowbits, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream,
+                           d->row_offs, n_rows, total, (unsigned long long *)d_bits,
+                           (u32 *)d_words);
+        hipLaunchKernelGGL(k_rsort_tiles, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                           d->keys, d->has, total, (u32)((flags & UA_SORT_DESC) != 0), d_bits,
+                           d->row_offs, n_rows, d_key[0], d_tag[0], d_trows);
+        /* the host knows only total: a round past the longest row's returns at once */
+        for (u32 k = 0; k < rounds; k++)
+            hipLaunchKernelGGL(k_rsort_round, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                               d->row_offs, n_rows, total, d_trows, (const u32 *)d_words, k,
+                               d_key[k & 1], d_tag[k & 1], d_key[(k + 1) & 1],
+                               d_tag[(k + 1) & 1]);
+        launches += 2 + rounds;
+    }
+    hipLaunchKernelGGL(k_rsort_page, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, d->row_offs,
+                       n_rows, total, d_key[0], d_tag[0], d_key[1], d_tag[1], (u32)sorted,
+                       (u32)flags, (int)d->count, (int)d->offset, d_len, d_rstart,
+                       d->out_ms_offs, d_bad);
+    if ((rc = ws_scan(c, d_len, n_rows + 1, d_offs))) return rc;
+    const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+    hipLaunchKernelGGL(k_rsort_offs, dim3(rgrid), dim3(UA_BLOCK), 0, c->stream, n_rows, d_offs,
+                       d_part, d_bad, d->out_row_offs, d_words + 1);
+    launches += 4;
+    const u64 wcap = d->cap_vals < total ? d->cap_vals : total; /* a page never grows a row */
+    if (!count_only && wcap) {
+        hipLaunchKernelGGL(k_rsort_write, dim3((u32)((wcap + UA_BLOCK - 1) / UA_BLOCK)),
+                           dim3(UA_BLOCK), 0, c->stream, d->vals, d->row_offs, n_rows, total,
+                           d_tag[0], d_tag[1], (u32)sorted, d_offs, d_part, d_rstart, d_bad,
+                           d->out_vals, d->out_src, wcap);
+        launches += 1;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    u64 need = 0;
+    HIP_TRY(hipMemcpyAsync(&need, d_words + 1, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
+    const u64 written = count_only ? 0 : (need < d->cap_vals ? need : d->cap_vals);
+    c->bytes_algo += in_bytes + 8 * (n_rows + 1) + 8 * written + (d->out_src ? 8 * written : 0);
+    *out_total = need;
+    return (!count_only && need > d->cap_vals) ? UA_ERR_INVALID : UA_OK;
+}
+
+/* host-pointer form of ua_rows_sort_dev: total is row_offs[n_rows].  Upload,
+ * one device call, download the offsets and what fits the capacity. */
+extern "C" int ua_rows_sort(ua_ctx *c, const uint64_t *vals, const uint64_t *row_offs,
+                            uint64_t n_rows, const uint64_t *keys, const uint8_t *has,
+                            uint64_t flags, int32_t count, int32_t offset, uint64_t *out_vals,
+                            uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_src,
+                            int32_t *out_ms_offs, uint64_t *out_total) {
+    if (!c || !out_total || !out_row_offs) return UA_ERR_INVALID;
+    if (n_rows && !row_offs) return UA_ERR_INVALID;
+    if (n_rows >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    const u64 total = n_rows ? row_offs[n_rows] : 0;
+    if (total && !vals) return UA_ERR_INVALID;
+    if (total >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    if (!keys && (flags || has)) return UA_ERR_INVALID;
+    if (flags & ~(u64)(UA_SORT_DESC | UA_SORT_MULTI | UA_SORT_DROP_NULLS)) return UA_ERR_INVALID;
+    if ((flags & UA_SORT_MULTI) && (flags & UA_SORT_DROP_NULLS)) return UA_ERR_INVALID;
+    if (out_ms_offs && !(flags & UA_SORT_MULTI)) return UA_ERR_INVALID;
+    if (out_src && !out_vals) return UA_ERR_INVALID;
+    if (!out_vals && cap_vals) return UA_ERR_INVALID;
+    if (cap_vals >= ((u64)1 << 60)) return UA_ERR_INVALID;
+    const bool count_only = !out_vals;
+    const u64 cb = std::min(cap_vals, total); /* the device never needs more */
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_H* reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    if ((rc = ws_reserve(c, WS_HU, (2 * total + nro) * sizeof(u64) + 16))) return rc;
+    if ((rc = ws_reserve(c, WS_HV, total + 16))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (nro + 2 * cb) * sizeof(u64) + n_rows * sizeof(int32_t) + 16)))
+        return rc;
+    u64 *d_vals = (u64 *)c->ws[WS_HU], *d_keys = d_vals + total, *d_ro = d_keys + total;
+    u8 *d_has = (u8 *)c->ws[WS_HV];
+    u64 *d_oro = (u64 *)c->ws[WS_HOUT], *d_ov = d_oro + nro, *d_os = d_ov + cb;
+    int32_t *d_ms = (int32_t *)(d_os + cb);
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(d_vals, vals, total * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+        if (keys)
+            HIP_TRY(hipMemcpyAsync(d_keys, keys, total * sizeof(u64), hipMemcpyHostToDevice,
+                                   c->stream));
+        if (has) HIP_TRY(hipMemcpyAsync(d_has, has, total, hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_rows)
+        HIP_TRY(hipMemcpyAsync(d_ro, row_offs, nro * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    else
+        HIP_TRY(hipMemsetAsync(d_ro, 0, sizeof(u64), c->stream));
+    ua_drowsort d = {};
+    d.vals = d_vals;
+    d.row_offs = d_ro;
+    d.n_rows = n_rows;
+    d.total = total;
+    d.keys = keys ? d_keys : nullptr;
+    d.has = has ? d_has : nullptr;
+    d.flags = flags;
+    d.count = count;
+    d.offset = offset;
+    d.out_vals = count_only ? nullptr : d_ov;
+    d.cap_vals = count_only ? 0 : cb;
+    d.out_row_offs = d_oro;
+    d.out_src = out_src ? d_os : nullptr;
+    d.out_ms_offs = out_ms_offs ? d_ms : nullptr;
+    u64 need = 0;
+    rc = ua_rows_sort_dev(c, &d, &need);
+    if (rc && rc != UA_ERR_INVALID) return rc;
+    if (rc == UA_ERR_INVALID && need == 0) return rc; /* rejected */
+    *out_total = need;
+    HIP_TRY(hipMemcpyAsync(out_row_offs, d_oro, nro * sizeof(u64), hipMemcpyDeviceToHost,
+                           c->stream));
+    if (out_ms_offs && n_rows)
+        HIP_TRY(hipMemcpyAsync(out_ms_offs, d_ms, n_rows * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, c->stream));
+    if (!count_only && need <= cap_vals && need) {
+        HIP_TRY(hipMemcpyAsync(out_vals, d_ov, need * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+        if (out_src)
+            HIP_TRY(hipMemcpyAsync(out_src, d_os, need * sizeof(u64), hipMemcpyDeviceToHost,
+                                   c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return (!count_only && need > cap_vals) ? UA_ERR_INVALID : UA_OK;
+}
 
 struct ua_owned_pack {
     std::vector<ua_block> blocks;

@@ -7,6 +7,9 @@ uidalgo engine — every heavy step runs on the GPU through the C-ABI:
    ONE batched segmented sort (`ua_sort_segments_dev`) over packed
    (key32 << 32 | row_position) u64 keys; pagination (paginate :740,
    x.PageRange x/x.go:815) is O(log) host logic on the sorted rows.
+   sort_rows_without_index is its CSR form: one `ua_rows_sort_dev` call over
+   the matrix the other row calls produce, 64-bit keys, pagination on the
+   device, a CSR matrix out.
  - sort_with_index (worker/sort.go:189-375): each index bucket intersects
    with every still-unfilled UidMatrix row as ONE batched intersect grid
    (`ua_intersect_batch_dev` — the engine form of pl.Uids(Intersect),
@@ -92,6 +95,20 @@ def sort_without_index(eng, uid_matrix, keys_of, offset, count, desc=False,
             ms_offsets.append(offset - start if start < offset else 0)
         rows.append(uids[start:end])
     return rows, ms_offsets
+
+
+def sort_rows_without_index(eng, vals, row_offs, keys, has, offset, count, desc=False,
+                            multi=False):
+    """sortWithoutIndex (sort.go:139-189) over a device-resident CSR matrix:
+    the CSR form of sort_without_index, one engine call (`ua_rows_sort_dev`)
+    and no host work per row.  vals, row_offs and keys (parallel to vals, u64
+    bits) are CUDA int64 tensors, has a CUDA uint8/bool tensor or None (every
+    element has a key).  Returns (out_vals, out_row_offs, ms_offs) as device
+    tensors — the CSR matrix `union_rows` and `filter_rows` take; ms_offs is
+    the int32 multiSortOffsets tensor, or None unless multi."""
+    res = eng.sort_rows(vals, row_offs, keys=keys, has=has, count=count, offset=offset,
+                        desc=desc, multi=multi)
+    return res[0], res[1], (res[2] if multi else None)
 
 
 def sort_with_index(eng, uid_matrix, buckets, offset, count, multi=False,

@@ -608,6 +608,112 @@ typedef struct {
 int ua_rows_encode_dev(ua_ctx *, const ua_drowenc *, uint64_t *n_blocks,
                        uint64_t *deltas_bytes);
 
+/* Sort and paginate every row of a CSR UID matrix by per-element keys in ONE
+ * call (since v19): CSR matrix in, CSR matrix out, device
+ * resident, one sync, nothing per row on the host.  It is the step between
+ * ua_rows_filter_dev and ua_rows_union_dev that the reference runs once per row
+ * for every ordered or paginated block (orderasc:, first:, offset:):
+ *   applyPagination            query/query.go:2493-2507 (x.PageRange per row)
+ *   applyOrderAndPagination    query/query.go:2511-2578 -> worker.SortOverNetwork
+ *     -> sortWithoutIndex      worker/sort.go:139-187
+ *        sortByValue           worker/sort.go:775-821
+ *        paginate              worker/sort.go:740-772
+ *   sortAndPaginateUsingVar    query/query.go:2697-2738
+ *   the cascade paginations    query/query.go:1483-1487, 3006-3010
+ *   x.PageRange                x/x.go:815-844
+ *
+ * Per row r (offsets clamped to total), n elements e_0 .. e_{n-1} in input order:
+ *  1. keys == NULL: S is the row as it is (applyPagination, the cascades).
+ *  2. Otherwise V = the elements with has != 0 (all when has == NULL), ordered
+ *     by key as unsigned 64-bit, ascending, or descending with UA_SORT_DESC;
+ *     ties by input position ASCENDING IN BOTH DIRECTIONS.  N = the other
+ *     elements in input order.  The reference's types.Sort is unstable, so it
+ *     leaves tie order open; position order is this project's refinement and
+ *     is uid-ascending on uid-sorted rows, as in oracle/sortref.py.
+ *  3. Without UA_SORT_DROP_NULLS, S = V then N (sortByValue appends the nulls
+ *     whether ascending or descending, sort.go:813).
+ *  4. With UA_SORT_DROP_NULLS, S = V (sortAndPaginateUsingVar,
+ *     query.go:2709-2716); when V is empty the row stays exactly as it was,
+ *     all n elements (the reference's `continue`, query.go:2718-2720).
+ *  5. (start, end) = x.PageRange(count, offset, len(S)), word for word:
+ *     count < 0 takes the last -count (clamped, offset ignored), offset < 0
+ *     counts as 0, offset > len gives an empty page, count == 0 means "to the
+ *     end".
+ *  6. With UA_SORT_MULTI (len(ts.Order) > 1, sort.go:748-769) the page grows
+ *     over equal keys at both edges, OVER V ONLY: while 0 < start < |V| and
+ *     key(S[start]) == key(S[start-1]) start--; while end < |V| and
+ *     key(S[end-1]) == key(S[end]) end++.  A null equals nothing: types.Equal
+ *     on a types.Val{} reports false or an error, never true.
+ *     oracle/sortref.py treats two nulls as equal; the two differ only when a
+ *     page edge lies inside the null tail under UA_SORT_MULTI.  The extension
+ *     is two binary searches in the sorted run, never a walk.
+ *  7. Out row r = S[start:end]; out_src[o] = the flat INPUT index of output
+ *     element o (so facets and values can be reordered without the IndexOf
+ *     loop of query.go:2561-2569, and multiSortVals fetched);
+ *     out_ms_offs[r] = start < offset ? offset - start : 0 (sort.go:170-178).
+ * Rows need not be uid-sorted and may hold duplicate uids.  0 and UINT64_MAX
+ * are ordinary keys and uids, also under UA_SORT_DESC.
+ *
+ * Capacity, by the family's rule: *out_total and out_row_offs are always the
+ * REQUIRED and complete values.  Every store is bounded by cap_vals.  A short
+ * cap_vals with non-NULL out_vals returns UA_ERR_INVALID, outputs untouched
+ * past the capacity.  Count-only form: out_vals NULL with cap_vals 0; no sort
+ * runs when the lengths do not depend on the order (keys == NULL, or neither
+ * UA_SORT_MULTI nor UA_SORT_DROP_NULLS).
+ *
+ * Rejected with UA_ERR_INVALID before the context is touched, nothing
+ * written: a null ctx, desc, out_total or out_row_offs; null vals with
+ * total > 0; null row_offs with n_rows > 0; n_rows == 0 with total != 0;
+ * flags != 0 or a non-NULL has with keys == NULL; unknown flag bits;
+ * UA_SORT_MULTI together with UA_SORT_DROP_NULLS (no reference caller has
+ * both); out_ms_offs without UA_SORT_MULTI; out_src with NULL out_vals; NULL
+ * out_vals with cap_vals > 0; any output overlapping an input or another
+ * output; total >= 2^31 or n_rows >= 2^31 (an element index plus the null bit
+ * share 32 bits); cap_vals >= 2^60.  total == 0 and n_rows == 0 are valid.
+ *
+ * Memory safety does not depend on the data: row_offs entries are clamped to
+ * total; a row_offs that is not monotone gives unspecified rows, never an
+ * out-of-range access: when a clamped entry lies below its predecessor every
+ * row is published empty (*out_total == 0), so rows never overlap and
+ * *out_total <= total always holds; every index read from a record is clamped
+ * below total; out_row_offs is a scan of the row lengths and out_vals
+ * receives exactly what it counts.  Elements past row_offs[n_rows] belong to
+ * no row and are left out.
+ *
+ * Engine scratch: 24 bytes per element (two buffers of an 8-byte key and a
+ * 4-byte tag), one bit per element for the row starts, 8 bytes per 2048-element
+ * tile, 16 bytes per row (length, first rank, scanned offset), the scan
+ * partials and 16 bytes of words.  The page-only form needs the per-row part
+ * only.
+ *
+ * Stats, with R = ceil(log2(ceil(total / 2048))): 6 + R launches for a sort
+ * without the write pass (row bits, tile sort, R rounds, page, two scan
+ * kernels, offsets), 7 + R with it; 4 and 5 for the page-only form, for
+ * total == 0 and for a count-only call that needs no sort (the write pass is
+ * also skipped when min(cap_vals, total) == 0).  kernel_ms is the whole
+ * sequence.  bytes_algorithmic grows by input plus output: 8*total for vals,
+ * 8*total for keys if given, total for has if given, 8*(n_rows+1) for each
+ * offset array, 8 per stored output element, plus 8 per stored output element
+ * for out_src. */
+enum { UA_SORT_DESC = 1, UA_SORT_MULTI = 2, UA_SORT_DROP_NULLS = 4 };
+typedef struct {
+    const uint64_t *vals;       /* device [total]: rows concatenated */
+    const uint64_t *row_offs;   /* device [n_rows+1] */
+    uint64_t n_rows, total;
+    const uint64_t *keys;       /* device [total], parallel to vals; NULL = page only */
+    const uint8_t *has;         /* device [total], nonzero = the element has a key;
+                                 * NULL = all have one */
+    uint64_t flags;             /* UA_SORT_*; must be 0 when keys == NULL */
+    int32_t count, offset;      /* ts.Count / ts.Offset, one 8-byte slot */
+    uint64_t *out_vals;         /* device [cap_vals]; NULL with cap_vals 0 = count only */
+    uint64_t cap_vals;
+    uint64_t *out_row_offs;     /* device [n_rows+1], always complete */
+    uint64_t *out_src;          /* optional, device [cap_vals]: flat INPUT index of
+                                 * every output element (the permutation) */
+    int32_t *out_ms_offs;       /* optional, device [n_rows]: multiSortOffsets */
+} ua_drowsort;                  /* 13 slots, 104 bytes */
+int ua_rows_sort_dev(ua_ctx *, const ua_drowsort *, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -733,6 +839,22 @@ int ua_rows_encode(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
                    uint32_t *num_uids, uint64_t *delta_offs, uint64_t cap_blocks,
                    uint8_t *deltas, uint64_t cap_deltas, uint64_t *row_block_base,
                    uint64_t *n_blocks, uint64_t *deltas_bytes);
+/* Order and pagination of every row of a UID matrix (applyPagination,
+ * query/query.go:2493-2507; sortWithoutIndex, worker/sort.go:139-187;
+ * sortAndPaginateUsingVar, query/query.go:2697-2738; x.PageRange,
+ * x/x.go:815-844) as ONE call: host form of ua_rows_sort_dev (since v19),
+ * same semantics, capacity rule and checks.  vals, row_offs, keys (or NULL)
+ * and has (or NULL) are host arrays, total = row_offs[n_rows]; out_vals
+ * (capacity cap_vals; NULL with cap_vals == 0 = count only), out_row_offs
+ * (n_rows+1), out_src (optional, cap_vals) and out_ms_offs (optional, n_rows)
+ * are host arrays.  The device works on its own buffers, so the outputs may
+ * overlap the inputs.  On a short cap_vals the offsets, out_ms_offs and
+ * *out_total are still delivered. */
+int ua_rows_sort(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
+                 uint64_t n_rows, const uint64_t *keys, const uint8_t *has,
+                 uint64_t flags, int32_t count, int32_t offset, uint64_t *out_vals,
+                 uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_src,
+                 int32_t *out_ms_offs, uint64_t *out_total);
 
 #ifdef __cplusplus
 }
