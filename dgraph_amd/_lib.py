@@ -147,6 +147,27 @@ class UaDRowSort(C.Structure):
     ]
 
 
+UA_TR_UNIQUE = 1
+
+
+class UaDRowTr(C.Structure):
+    _fields_ = [
+        ("vals", C.c_void_p),
+        ("row_offs", C.c_void_p),
+        ("n_rows", _u64),
+        ("total", _u64),
+        ("row_uids", C.c_void_p),
+        ("row_keep", C.c_void_p),
+        ("flags", _u64),
+        ("out_keys", C.c_void_p),
+        ("out_offs", C.c_void_p),
+        ("cap_keys", _u64),
+        ("out_vals", C.c_void_p),
+        ("out_src", C.c_void_p),
+        ("cap_vals", _u64),
+    ]
+
+
 class UaPTask(C.Structure):
     _fields_ = [
         ("v", C.c_void_p),
@@ -247,6 +268,11 @@ def lib():
             L.ua_rows_sort.argtypes = [
                 C.c_void_p, _u64p, _u64p, _u64, _u64p, _u8p, _u64, C.c_int32, C.c_int32,
                 _u64p, _u64, _u64p, _u64p, C.POINTER(C.c_int32), _u64p]
+        if L.ua_version() >= 20:  # an older library via UA_LIB_PATH (A/B runs)
+            L.ua_rows_transpose_dev.argtypes = [C.c_void_p, C.POINTER(UaDRowTr), _u64p, _u64p]
+            L.ua_rows_transpose.argtypes = [
+                C.c_void_p, _u64p, _u64p, _u64, _u64p, _u8p, _u64, _u64p, _u64p, _u64,
+                _u64p, _u64p, _u64, _u64p, _u64p]
         L.ua_intersect_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_merge_k_dev.argtypes = [C.c_void_p, _voidpp, _u64p, C.c_int, C.c_void_p, _u64p]
         L.ua_intersect_packed_dev.argtypes = [C.c_void_p, C.POINTER(UaDPack), _u64, C.c_void_p,

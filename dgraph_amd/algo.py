@@ -371,6 +371,80 @@ class Engine:
         offset) of every row as one call — sort_rows with keys=None."""
         return self.sort_rows(vals, row_offs, count=count, offset=offset)
 
+    def transpose_rows(self, vals, row_offs, row_uids=None, row_keep=None, unique=False,
+                       want_src=False, groups_only=False, count_only=False):
+        """The transpose of a CSR UID matrix in ONE call
+        (ua_rows_transpose_dev): src -> [dst...] into dst -> [src...], the
+        grouping dedup.addValue builds per edge (query/groupby.go:104-128,
+        formResult :195-260) and the postings rebuildReverseEdges adds one by
+        one (posting/index.go:1759-1791).  vals, row_offs and row_uids (the
+        rows' uids; None = the row index) are CUDA int64 tensors holding u64
+        bits, row_keep a CUDA uint8/bool tensor per row (nonzero = the row takes
+        part) or None.  Returns (keys, offs, vals[, src]): the distinct values
+        ascending, the CSR offsets of their groups, and per group the uids of
+        the rows holding the value in input order; src (want_src) is each
+        entry's flat input index.  unique keeps one entry per (value, row).
+        groups_only returns (keys, offs), count_only (n_groups, n_entries)."""
+        import torch
+        from dgraph_amd._lib import UA_TR_UNIQUE, UaDRowTr
+        dev = vals.device
+        total = vals.numel()
+        n_rows = row_offs.numel() - 1
+        if n_rows < 0:
+            raise ValueError("row_offs needs n_rows + 1 entries")
+        if row_uids is not None and row_uids.numel() != n_rows:
+            raise ValueError("row_uids needs one entry per row")
+        if row_keep is not None:
+            if row_keep.numel() != n_rows:
+                raise ValueError("row_keep needs one entry per row")
+            if row_keep.dtype == torch.bool:
+                row_keep = row_keep.view(torch.uint8)
+            if row_keep.dtype != torch.uint8:
+                raise ValueError("row_keep must be a uint8 or bool tensor")
+        if want_src and (groups_only or count_only):
+            raise ValueError("out_src comes with the full form only")
+        d = UaDRowTr()
+        d.vals = vals.data_ptr() if total else None
+        d.row_offs = row_offs.data_ptr()
+        d.n_rows = n_rows
+        d.total = total
+        d.row_uids = row_uids.data_ptr() if row_uids is not None and n_rows else None
+        d.row_keep = row_keep.data_ptr() if row_keep is not None and n_rows else None
+        d.flags = UA_TR_UNIQUE if unique else 0
+        keys = offs = out = src = None
+        if not count_only:  # both requirements are at most total
+            keys = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+            offs = torch.empty(total + 1, dtype=torch.int64, device=dev)
+            d.out_keys, d.out_offs, d.cap_keys = keys.data_ptr(), offs.data_ptr(), total
+            if not groups_only:
+                out = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+                d.out_vals, d.cap_vals = out.data_ptr(), total
+                if want_src:
+                    src = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+                    d.out_src = src.data_ptr()
+        ng, nt = _u64(), _u64()
+        check(lib().ua_rows_transpose_dev(self._ctx, C.byref(d), C.byref(ng), C.byref(nt)))
+        if count_only:
+            return ng.value, nt.value
+        res = [keys[:ng.value], offs[:ng.value + 1]]
+        if not groups_only:
+            res.append(out[:nt.value])
+            if want_src:
+                res.append(src[:nt.value])
+        return tuple(res)
+
+    def reverse_rows(self, dpb, mut_uids, mut_ops, row_mut_base, row_uids=None,
+                     block_size=256):
+        """A batched rebuildReverseEdges (posting/index.go:1759-1791) on the
+        device: decode_rows_mut with after = first = 0, transpose_rows with
+        unique=True, then encode_rows.  Takes decode_rows_mut's arguments and
+        the forward lists' uids (ascending; None = the row index).  Returns
+        (keys, arena): the uids that own a reverse list, ascending, and
+        encode_rows' arena with one pack per key."""
+        vals, row_offs = self.decode_rows_mut(dpb, mut_uids, mut_ops, row_mut_base)
+        keys, offs, rev = self.transpose_rows(vals, row_offs, row_uids=row_uids, unique=True)
+        return keys, self.encode_rows(rev, offs, block_size)
+
     # ---- packed (codec) path ----
     def upload_pack(self, bases, num_uids, delta_offs, deltas_blob, block_size):
         """Upload flat pack arrays (from encode_flat) -> DPack on this GPU."""
@@ -1238,6 +1312,60 @@ def paginate_uid_matrix(engine, rows, count, offset):
     """applyPagination (query/query.go:2493-2507): x.PageRange(count, offset)
     of every row as ONE call (ua_rows_sort without keys).  Returns the rows."""
     return sort_uid_matrix(engine, rows, None, count=count, offset=offset)[0]
+
+
+def transpose_uid_matrix(engine, rows, src_uids=None, keep=None, unique=False,
+                         want_src=False):
+    """The transpose of a UID matrix as ONE call (ua_rows_transpose): what
+    dedup.addValue (query/groupby.go:104-128) collects per edge and
+    rebuildReverseEdges (posting/index.go:1759-1791) adds per posting.  rows:
+    sequences of uids; src_uids: the rows' uids (None = the row index); keep:
+    one truth value per row (None = all).  Returns (keys, groups): the distinct
+    values ascending and, per key, the uids of the rows that hold it in input
+    order (one per (value, row) with unique); with want_src also each group's
+    flat input indices, as a third item."""
+    from dgraph_amd._lib import UA_TR_UNIQUE
+    n = len(rows)
+    rows = [_np_u64(r).ravel() for r in rows]
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([r.size for r in rows], dtype=np.uint64)
+    total = int(offs[n])
+    vals = np.ascontiguousarray(np.concatenate(rows)) if n else np.empty(0, np.uint64)
+    ru = kp = None
+    if src_uids is not None:
+        ru = _np_u64(src_uids).ravel()
+        if ru.size != n:
+            raise ValueError("src_uids needs one uid per row")
+    if keep is not None:
+        kp = np.ascontiguousarray(np.asarray(keep, dtype=bool).ravel().astype(np.uint8))
+        if kp.size != n:
+            raise ValueError("keep needs one entry per row")
+    keys = np.empty(max(total, 1), dtype=np.uint64)
+    goffs = np.empty(total + 1, dtype=np.uint64)
+    out = np.empty(max(total, 1), dtype=np.uint64)
+    src = np.empty(max(total, 1), dtype=np.uint64) if want_src else None
+    ng, nt = _u64(), _u64()
+    check(lib().ua_rows_transpose(
+        engine._ctx, _hptr(vals), _hptr(offs), n,
+        _hptr(ru) if ru is not None and n else None,
+        kp.ctypes.data_as(C.POINTER(C.c_uint8)) if kp is not None and n else None,
+        UA_TR_UNIQUE if unique else 0, _hptr(keys), _hptr(goffs), total, _hptr(out),
+        _hptr(src) if want_src else None, total, C.byref(ng), C.byref(nt)))
+    k = ng.value
+    res = (keys[:k].copy(), _split_rows(out, goffs[:k + 1]))
+    if want_src:
+        res += (_split_rows(src, goffs[:k + 1]),)
+    return res
+
+
+def group_by_uid(engine, rows, src_uids, keep=None):
+    """groupby over one uid predicate (formResult, query/groupby.go:195-260):
+    rows[i] is the child's UidMatrix row of src_uids[i], keep[i] whether
+    src_uids[i] is in the parent's list (the `IndexOf(ul, srcUid) < 0`
+    test).  Returns [(dst, [src...])...] with dst ascending, the groups
+    formGroups consumes at depth 1; count(uid) of a group is its length."""
+    keys, groups = transpose_uid_matrix(engine, rows, src_uids, keep)
+    return [(int(k), [int(x) for x in g]) for k, g in zip(keys, groups)]
 
 
 def rollup_rows(engine, packs, muts, block_size=256):

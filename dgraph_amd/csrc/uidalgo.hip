@@ -3924,6 +3924,331 @@ __global__ __launch_bounds__(UA_BLOCK) void k_rsort_write(
     if (out_src) out_src[o] = src;
 }
 
+/* ==================== kernels: transpose a CSR UID matrix ====================
+ * src -> [dst...] into dst -> [src...] in one call: the
+ * grouping of dedup.addValue (query/groupby.go:104-128) that formResult
+ * (:195-260) and fillGroupedVars (:265-361) run per edge, and the reverse
+ * postings of rebuildReverseEdges (posting/index.go:1759-1791, one
+ * addReverseMutation :276-298 per posting).
+ *
+ * A record is (value, tag) with tag = dead << 31 | flat input index, in the row
+ * sort's layout and under its order d_rs_less: live before dead, then value,
+ * then flat index.  That is a total order over the FLAT array, so there is no
+ * row segmentation: k_rtr_tiles sorts each tile, round k of k_rtr_round merges
+ * groups of 2^k tiles pairwise between the two record buffers, and after
+ * ceil(log2 ntiles) rounds the live records are one run ordered by (value,
+ * flat index).  A group is a run of equal values, already in addValue's append
+ * order.  k_rtr_groups<false> counts group heads and kept entries per tile of
+ * that run, one scan runs over both count arrays, k_rtr_groups<true> is the
+ * same code with the scanned bases and stores the four outputs. */
+
+#define UA_TR_DEAD UA_RS_NULL /* tag: the element takes no part */
+
+/* One workgroup per UA_RTILE flat elements.  Waves 0 and 1 bracket the rows of
+ * the tile's first and last element (first row_offs entry above each); a
+ * thread then searches only that bracket.  An element is live when its row r
+ * holds it (row_offs[r] <= p < row_offs[r + 1], checked, so a row_offs that is
+ * not monotone gives a dead element, never a wrong index), p lies below
+ * min(row_offs[n_rows], total) and row_keep admits r.  Comparing the raw
+ * row_offs entries against p < total is comparing the clamped ones.  erow[p]
+ * gets the row (0 for a dead element), the sorted tile goes to the tile's own
+ * flat positions.  Padding past total sorts last. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rtr_tiles(
+    const u64 *__restrict__ vals, u64 total, const u64 *__restrict__ row_offs, u64 n_rows,
+    const u8 *__restrict__ row_keep, u64 *__restrict__ rkey, u32 *__restrict__ rtag,
+    u32 *__restrict__ erow) {
+    __shared__ u64 s_key[UA_RTILE];
+    __shared__ u32 s_tag[UA_RTILE];
+    __shared__ u32 s_br[2];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u64 t0 = (u64)blockIdx.x * UA_RTILE;
+    const int len = (int)((total - t0 < UA_RTILE) ? total - t0 : UA_RTILE); /* t0 < total */
+    if (wv < 2) {
+        const u64 p = (wv == 0) ? t0 : t0 + (u64)len - 1;
+        u64 idx = d_wave_lower_bound(row_offs, n_rows + 1, p + 1, lane); /* first > p */
+        if (idx > n_rows + 1) idx = n_rows + 1;
+        if (lane == 0) s_br[wv] = (u32)idx; /* n_rows < 2^31 */
+    }
+    __syncthreads();
+    const u32 br0 = s_br[0], br1 = s_br[1];
+    u64 lim = row_offs[n_rows];
+    lim = lim < total ? lim : total;
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int i = s * UA_BLOCK + tid;
+        u64 k = ~(u64)0;
+        u32 tg = 0xffffffffu;
+        if (i < len) {
+            const u64 p = t0 + i;
+            u32 lo = br0, hi = br1; /* br0 > br1 (broken row_offs): no probe */
+            while (lo < hi) {
+                u32 m = lo + ((hi - lo) >> 1); /* m < br1 <= n_rows + 1 */
+                if (row_offs[m] > p) hi = m;
+                else lo = m + 1;
+            }
+            u32 r = 0;
+            bool live = false;
+            if (lo >= 1 && lo <= n_rows) {
+                r = lo - 1;
+                live = p < lim && row_offs[r] <= p && p < row_offs[r + 1] &&
+                       (!row_keep || row_keep[r] != 0);
+            }
+            erow[p] = live ? r : 0;
+            k = live ? vals[p] : 0;
+            tg = (live ? 0u : UA_TR_DEAD) | (u32)p; /* p < 2^31 */
+        }
+        s_key[i] = k;
+        s_tag[i] = tg;
+    }
+    __syncthreads();
+    /* the bitonic network of k_sort_chunks under d_rs_less */
+    for (int k = 2; k <= UA_RTILE; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < UA_RTILE; i += UA_BLOCK) {
+                int p = i ^ j;
+                if (p > i) {
+                    bool up = ((i & k) == 0);
+                    u64 kx = s_key[i], ky = s_key[p];
+                    u32 tx = s_tag[i], ty = s_tag[p];
+                    bool gt = d_rs_less(ky, ty, kx, tx);
+                    if (gt == up) {
+                        s_key[i] = ky;
+                        s_key[p] = kx;
+                        s_tag[i] = ty;
+                        s_tag[p] = tx;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const int i = s * UA_BLOCK + tid;
+        if (i < len) { /* the len real records sort before the padding */
+            rkey[t0 + i] = s_key[i];
+            rtag[t0 + i] = s_tag[i];
+        }
+    }
+}
+
+/* Round k, one workgroup per flat tile: the records of the tile's own flat
+ * positions in the merge of its group pair (2^k tiles each, the last group of
+ * the array may be shorter), from src into dst: two diagonal splits in global
+ * memory, at most UA_RTILE records into LDS, each ranked against the other
+ * side, a coalesced store.  A group without a partner is copied.  The host
+ * enqueues exactly ceil(log2 ntiles) rounds, so every round has work.  All
+ * that decides a barrier comes from blockIdx and the kernel arguments. */
+__global__ __launch_bounds__(UA_BLOCK) void k_rtr_round(
+    u64 total, u32 ntiles, u32 k, const u64 *__restrict__ skey, const u32 *__restrict__ stag,
+    u64 *__restrict__ dkey, u32 *__restrict__ dtag) {
+    __shared__ u64 s_key[UA_RTILE];
+    __shared__ u32 s_tag[UA_RTILE];
+    __shared__ u32 s_sp[2];
+    const int tid = threadIdx.x;
+    const u32 t = blockIdx.x; /* t < ntiles <= 2^20 */
+    const u32 o0 = t * UA_RTILE;
+    const u32 o1 = (total - o0 < UA_RTILE) ? (u32)total : o0 + UA_RTILE;
+    const u32 cnt = o1 - o0;
+    const u32 s0 = (t >> (k + 1)) << (k + 1), smid = s0 + (1u << k);
+    if (smid >= ntiles) { /* uniform: no partner */
+        for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+            dkey[o0 + i] = skey[o0 + i];
+            dtag[o0 + i] = stag[o0 + i];
+        }
+        return;
+    }
+    const u64 s1w = (u64)s0 + ((u64)2 << k);
+    const u32 L0 = s0 * UA_RTILE, L1 = smid * UA_RTILE;
+    const u32 R1 = s1w >= ntiles ? (u32)total : (u32)s1w * UA_RTILE;
+    const u32 na = L1 - L0, nb = R1 - L1; /* L0 <= o0 < o1 <= R1 */
+    if (tid < 2)
+        s_sp[tid] = d_rs_split(skey + L0, stag + L0, na, skey + L1, stag + L1, nb,
+                               (tid == 0 ? o0 : o1) - L0);
+    __syncthreads();
+    const u32 i0 = s_sp[0], i1 = s_sp[1];
+    const u32 j0 = (o0 - L0) - i0;
+    const u32 ca = i1 - i0; /* A records; the other cnt - ca come from B at j0 */
+    for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+        u32 g = i < ca ? L0 + i0 + i : L1 + j0 + (i - ca);
+        s_key[i] = skey[g];
+        s_tag[i] = stag[g];
+    }
+    __syncthreads();
+    u64 mk[UA_RSTEPS];
+    u32 mt[UA_RSTEPS], mr[UA_RSTEPS];
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const u32 i = (u32)s * UA_BLOCK + tid;
+        mr[s] = UA_RTILE;
+        if (i < cnt) {
+            mk[s] = s_key[i];
+            mt[s] = s_tag[i];
+            /* rank = own index in its part + records of the other part below it */
+            u32 lo, hi, own;
+            if (i < ca) { lo = ca; hi = cnt; own = i; }
+            else { lo = 0; hi = ca; own = i - ca; }
+            const u32 base = lo;
+            while (lo < hi) {
+                u32 m = (lo + hi) >> 1;
+                if (d_rs_less(s_key[m], s_tag[m], mk[s], mt[s])) lo = m + 1;
+                else hi = m;
+            }
+            mr[s] = own + (lo - base);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++)
+        if (mr[s] < cnt) {
+            s_key[mr[s]] = mk[s];
+            s_tag[mr[s]] = mt[s];
+        }
+    __syncthreads();
+    for (u32 i = tid; i < cnt; i += UA_BLOCK) {
+        dkey[o0 + i] = s_key[i];
+        dtag[o0 + i] = s_tag[i];
+    }
+}
+
+/* One workgroup per tile of the sorted run in UA_RSTEPS coalesced 256-wide
+ * steps; a record's rank among the tile's heads (kept entries) is the count in
+ * the steps and waves before its own plus the ballot bits of the lanes below
+ * it.  head = live and (first or value != previous value);
+ * keep = live and not (unique and same value and same row as the previous
+ * record), so of equal (value, row) entries the lowest flat index stays.
+ * WRITE == false leaves the tile's head count in cnt[tile] and its keep count
+ * in cnt[ntiles + 1 + tile] (tile 0 also writes the two closing zeros) and
+ * adds both to words[0], words[1].  One exclusive scan over the 2 * (ntiles +
+ * 1) counts serves both: a head base is d_off(tile), a keep base d_off(ntiles
+ * + 1 + tile) - words[0].  WRITE == true repeats the flags and stores keys and
+ * group offsets below cap_keys (+ 1), entries below cap_vals.  Every flat
+ * index read from a tag is clamped below total and every row below n_rows. */
+template <bool WRITE>
+__global__ __launch_bounds__(UA_BLOCK) void k_rtr_groups(
+    const u64 *__restrict__ rkey, const u32 *__restrict__ rtag, const u32 *__restrict__ erow,
+    u64 total, u64 n_rows, u32 ntiles, u32 unique, u32 *__restrict__ cnt,
+    const u64 *__restrict__ offs, const u64 *__restrict__ part,
+    unsigned long long *__restrict__ words, const u64 *__restrict__ row_uids,
+    u64 *__restrict__ out_keys, u64 *__restrict__ out_offs, u64 cap_keys,
+    u64 *__restrict__ out_vals, u64 *__restrict__ out_src, u64 cap_vals) {
+    __shared__ u32 s_ch[UA_RSTEPS][UA_BLOCK / 64], s_ck[UA_RSTEPS][UA_BLOCK / 64];
+    __shared__ u32 s_tot[2];
+    static_assert(UA_RSTEPS * (UA_BLOCK / 64) == 32, "one half wave scans the counts");
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u32 tile = blockIdx.x;
+    const u64 t0 = (u64)tile * UA_RTILE;
+    const bool rows = unique || (WRITE && out_vals);
+    const u64 below = ((u64)1 << lane) - 1;
+    u64 ek[UA_RSTEPS];
+    u32 es[UA_RSTEPS], er[UA_RSTEPS];
+    u32 lh[UA_RSTEPS], lk[UA_RSTEPS]; /* heads and kept entries in the lanes below */
+    u32 hm = 0, km = 0;
+#pragma unroll
+    for (int s = 0; s < UA_RSTEPS; s++) {
+        const u64 p = t0 + (u64)s * UA_BLOCK + tid;
+        const bool in = p < total;
+        u32 tg = UA_TR_DEAD;
+        u64 kk = 0;
+        if (in) {
+            tg = rtag[p];
+            kk = rkey[p];
+        }
+        /* the previous record: the lane below holds it, lane 0 reads it */
+        u64 pk = __shfl_up(kk, 1);
+        u32 pt = __shfl_up(tg, 1);
+        if (lane == 0) {
+            pt = UA_TR_DEAD;
+            pk = 0;
+            if (in && p > 0) {
+                pt = rtag[p - 1];
+                pk = rkey[p - 1];
+            }
+        }
+        const bool live = !(tg & UA_TR_DEAD);
+        const bool same = !(pt & UA_TR_DEAD) && kk == pk;
+        u64 src = tg & UA_RS_IDX;
+        if (src >= total) src = total - 1; /* total > 0 */
+        u32 row = 0;
+        bool dup = false;
+        if (live && rows) row = erow[src];
+        if (live && unique && same) {
+            u64 ps = pt & UA_RS_IDX;
+            if (ps >= total) ps = total - 1;
+            dup = erow[ps] == row;
+        }
+        const bool head = live && !same;
+        const bool keep = live && !dup;
+        const u64 bh = __ballot(head), bk = __ballot(keep);
+        lh[s] = (u32)__popcll(bh & below);
+        lk[s] = (u32)__popcll(bk & below);
+        if (lane == 0) {
+            s_ch[s][wv] = (u32)__popcll(bh);
+            s_ck[s][wv] = (u32)__popcll(bk);
+        }
+        hm |= (head ? 1u : 0u) << s;
+        km |= (keep ? 1u : 0u) << s;
+        ek[s] = kk;
+        es[s] = (u32)src;
+        er[s] = row;
+        /* keep the step's flags and counts in vector registers: as lane masks
+         * sixteen ballots and conditions live to the stores outgrow the scalar file */
+        asm volatile("" : "+v"(lh[s]), "+v"(lk[s]), "+v"(hm), "+v"(km));
+    }
+    __syncthreads();
+    /* records run by (step, wave, lane): wave 0 scans the 32 head counts in its
+     * lower half and the 32 keep counts in its upper half, exclusive, in place */
+    if (wv == 0) {
+        u32 *sc = lane < 32 ? &s_ch[0][0] : &s_ck[0][0];
+        const int q = lane & 31;
+        const u32 c = sc[q];
+        u32 incl = c;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            u32 x = __shfl_up(incl, o);
+            if (q >= o) incl += x;
+        }
+        sc[q] = incl - c;
+        if (q == 31) s_tot[lane >> 5] = incl;
+    }
+    __syncthreads();
+    const u32 M = ntiles + 1;
+    if constexpr (!WRITE) {
+        if (tid == 0) {
+            const u32 toth = s_tot[0], totk = s_tot[1];
+            cnt[tile] = toth;
+            cnt[M + tile] = totk;
+            if (tile == 0) {
+                cnt[ntiles] = 0;
+                cnt[M + ntiles] = 0;
+            }
+            atomicAdd(&words[0], (unsigned long long)toth);
+            atomicAdd(&words[1], (unsigned long long)totk);
+        }
+    } else {
+        const u64 ng = words[0], nt = words[1];
+        const u64 gb = d_off(offs, part, tile);
+        const u64 eb = d_off(offs, part, (u64)M + tile) - ng;
+#pragma unroll
+        for (int s = 0; s < UA_RSTEPS; s++) {
+            if (!((km >> s) & 1u)) continue; /* a head is always kept */
+            const u64 e = eb + s_ck[s][wv] + lk[s];
+            if ((hm >> s) & 1u) {
+                const u64 g = gb + s_ch[s][wv] + lh[s];
+                if (g < cap_keys) out_keys[g] = ek[s];
+                if (g <= cap_keys) out_offs[g] = e;
+            }
+            if (out_vals && e < cap_vals) {
+                u64 r = er[s];
+                if (r >= n_rows) r = n_rows - 1; /* n_rows >= 1: total > 0 */
+                out_vals[e] = row_uids ? row_uids[r] : r;
+                if (out_src) out_src[e] = es[s];
+            }
+        }
+        if (tile == 0 && tid == 0 && ng <= cap_keys) out_offs[ng] = nt;
+    }
+}
+
 /* ==================== host shim ==================== */
 
 static thread_local hipError_t g_last_hip = hipSuccess;
@@ -3973,7 +4298,7 @@ extern "C" const char *ua_strerror(int code) {
     }
 }
 
-extern "C" int ua_version(void) { return 19; }
+extern "C" int ua_version(void) { return 20; }
 
 /* streams and events; on failure the caller destroys c */
 static int ctx_init(ua_ctx *c) {
@@ -6550,6 +6875,203 @@ extern "C" int ua_rows_sort(ua_ctx *c, const uint64_t *vals, const uint64_t *row
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return (!count_only && need > cap_vals) ? UA_ERR_INVALID : UA_OK;
+}
+
+/* ---- transpose a CSR UID matrix ----
+ * dedup.addValue's grouping (query/groupby.go:104-128, formResult :195-260,
+ * fillGroupedVars :265-361) and rebuildReverseEdges (posting/index.go:1759-1791)
+ * over a whole matrix in one call: tile sort -> merge rounds -> flags -> scan
+ * (-> write), one sync, two u64 back to the host.  The argument checks come
+ * before c is touched. */
+extern "C" int ua_rows_transpose_dev(ua_ctx *c, const ua_drowtr *d, uint64_t *n_groups,
+                                     uint64_t *out_total) {
+    if (!c || !d || !n_groups || !out_total) return UA_ERR_INVALID;
+    const u64 total = d->total, n_rows = d->n_rows, flags = d->flags;
+    if (total && !d->vals) return UA_ERR_INVALID;
+    if (n_rows && !d->row_offs) return UA_ERR_INVALID;
+    if (n_rows == 0 && total != 0) return UA_ERR_INVALID;
+    if (flags & ~(u64)UA_TR_UNIQUE) return UA_ERR_INVALID;
+    if (!d->out_keys != !d->out_offs) return UA_ERR_INVALID;
+    if (!d->out_keys && d->cap_keys) return UA_ERR_INVALID;
+    if (!d->out_vals && d->cap_vals) return UA_ERR_INVALID;
+    if (d->out_src && !d->out_vals) return UA_ERR_INVALID;
+    if (d->out_vals && !d->out_keys) return UA_ERR_INVALID;
+    /* a flat index and the dead bit share a 32-bit tag */
+    if (total >= ((u64)1 << 31) || n_rows >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    if (d->cap_keys >= ((u64)1 << 60) || d->cap_vals >= ((u64)1 << 60))
+        return UA_ERR_INVALID; /* byte sizes below stay in u64 */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } rg[] = {{d->vals, total * sizeof(u64)},
+              {d->row_offs, d->row_offs ? (n_rows + 1) * sizeof(u64) : 0},
+              {d->row_uids, n_rows * sizeof(u64)},
+              {d->row_keep, n_rows},
+              {d->out_keys, d->cap_keys * sizeof(u64)},
+              {d->out_offs, (d->cap_keys + 1) * sizeof(u64)},
+              {d->out_vals, d->cap_vals * sizeof(u64)},
+              {d->out_src, d->cap_vals * sizeof(u64)}};
+    const int n_rg = (int)(sizeof(rg) / sizeof(rg[0]));
+    for (int a = 4; a < n_rg; a++) /* every output against the inputs and the other outputs */
+        for (int b = 0; b < a; b++)
+            if (rg[a].p && rg[b].p && ranges_overlap(rg[a].p, rg[a].bytes, rg[b].p, rg[b].bytes))
+                return UA_ERR_INVALID;
+
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    const bool groups = d->out_keys != nullptr; /* the full and the groups-only form */
+    const u64 ntiles = (total + UA_RTILE - 1) / UA_RTILE;
+    const u32 rounds = rsort_rounds(ntiles);
+    const u64 M = ntiles + 1;
+    int rc;
+    if ((rc = ws_reserve(c, WS_SCRATCH_A, (size_t)(total ? total : 1) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_SCRATCH_B, (size_t)(total ? total : 1) * 24))) return rc;
+    if ((rc = ws_reserve(c, WS_TCNT, (size_t)(2 * M) * sizeof(u32)))) return rc;
+    if ((rc = ws_reserve(c, WS_TOFF, (size_t)(2 * M) * sizeof(u64)))) return rc;
+    if ((rc = ws_reserve(c, WS_KLEN, 2 * sizeof(u64)))) return rc;
+    u32 *d_erow = (u32 *)c->ws[WS_SCRATCH_A];
+    u64 *d_key[2];
+    u32 *d_tag[2];
+    d_key[0] = (u64 *)c->ws[WS_SCRATCH_B];
+    d_key[1] = d_key[0] + total;
+    d_tag[0] = (u32 *)(d_key[1] + total);
+    d_tag[1] = d_tag[0] + total;
+    u32 *d_cnt = (u32 *)c->ws[WS_TCNT];
+    u64 *d_offs = (u64 *)c->ws[WS_TOFF];
+    unsigned long long *d_words = (unsigned long long *)c->ws[WS_KLEN]; /* groups, entries */
+    u64 launches = 0;
+
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(hipMemsetAsync(d_words, 0, 2 * sizeof(u64), c->stream));
+    if (total == 0) {
+        if (groups) HIP_TRY(hipMemsetAsync(d->out_offs, 0, sizeof(u64), c->stream));
+    } else {
+        const u32 unique = (u32)((flags & UA_TR_UNIQUE) != 0);
+        hipLaunchKernelGGL(k_rtr_tiles, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream, d->vals,
+                           total, d->row_offs, n_rows, d->row_keep, d_key[0], d_tag[0], d_erow);
+        for (u32 k = 0; k < rounds; k++)
+            hipLaunchKernelGGL(k_rtr_round, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                               total, (u32)ntiles, k, d_key[k & 1], d_tag[k & 1],
+                               d_key[(k + 1) & 1], d_tag[(k + 1) & 1]);
+        const u64 *fkey = d_key[rounds & 1];
+        const u32 *ftag = d_tag[rounds & 1];
+        hipLaunchKernelGGL(k_rtr_groups<false>, dim3((u32)ntiles), dim3(UA_BLOCK), 0, c->stream,
+                           fkey, ftag, d_erow, total, n_rows, (u32)ntiles, unique, d_cnt,
+                           (const u64 *)nullptr, (const u64 *)nullptr, d_words,
+                           (const u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr, (u64)0,
+                           (u64 *)nullptr, (u64 *)nullptr, (u64)0);
+        launches += 2 + rounds;
+        if (groups) {
+            if ((rc = ws_scan(c, d_cnt, 2 * M, d_offs))) return rc;
+            const u64 *d_part = (const u64 *)c->ws[WS_PARTIAL];
+            hipLaunchKernelGGL(k_rtr_groups<true>, dim3((u32)ntiles), dim3(UA_BLOCK), 0,
+                               c->stream, fkey, ftag, d_erow, total, n_rows, (u32)ntiles, unique,
+                               d_cnt, d_offs, d_part, d_words, d->row_uids, d->out_keys,
+                               d->out_offs, d->cap_keys, d->out_vals, d->out_src, d->cap_vals);
+            launches += 3;
+        }
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    u64 need[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(need, d_words, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    if ((rc = stats_add(c, c->ev[0], c->ev[1], launches))) return rc;
+    const u64 wk = groups ? std::min(need[0], d->cap_keys) : 0;
+    const u64 wv = d->out_vals ? std::min(need[1], d->cap_vals) : 0;
+    c->bytes_algo += 8 * total + 8 * (n_rows + 1) + (d->row_uids ? 8 * n_rows : 0) +
+                     (d->row_keep ? n_rows : 0) + (groups ? 8 * wk + 8 * (wk + 1) : 0) +
+                     8 * wv + (d->out_src ? 8 * wv : 0);
+    *n_groups = need[0];
+    *out_total = need[1];
+    const bool is_short = (groups && need[0] > d->cap_keys) ||
+                          (d->out_vals && need[1] > d->cap_vals);
+    return is_short ? UA_ERR_INVALID : UA_OK;
+}
+
+/* host-pointer form of ua_rows_transpose_dev: total is row_offs[n_rows].
+ * Upload, one device call, download what fits the capacities. */
+extern "C" int ua_rows_transpose(ua_ctx *c, const uint64_t *vals, const uint64_t *row_offs,
+                                 uint64_t n_rows, const uint64_t *row_uids,
+                                 const uint8_t *row_keep, uint64_t flags, uint64_t *out_keys,
+                                 uint64_t *out_offs, uint64_t cap_keys, uint64_t *out_vals,
+                                 uint64_t *out_src, uint64_t cap_vals, uint64_t *n_groups,
+                                 uint64_t *out_total) {
+    if (!c || !n_groups || !out_total) return UA_ERR_INVALID;
+    if (n_rows && !row_offs) return UA_ERR_INVALID;
+    if (n_rows >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    const u64 total = n_rows ? row_offs[n_rows] : 0;
+    if (total && !vals) return UA_ERR_INVALID;
+    if (total >= ((u64)1 << 31)) return UA_ERR_INVALID;
+    if (flags & ~(u64)UA_TR_UNIQUE) return UA_ERR_INVALID;
+    if (!out_keys != !out_offs) return UA_ERR_INVALID;
+    if (!out_keys && cap_keys) return UA_ERR_INVALID;
+    if (!out_vals && cap_vals) return UA_ERR_INVALID;
+    if (out_src && !out_vals) return UA_ERR_INVALID;
+    if (out_vals && !out_keys) return UA_ERR_INVALID;
+    if (cap_keys >= ((u64)1 << 60) || cap_vals >= ((u64)1 << 60)) return UA_ERR_INVALID;
+    const u64 ck = std::min(cap_keys, total), cv = std::min(cap_vals, total);
+
+    std::lock_guard<std::recursive_mutex> gop(c->mu); /* whole-op: WS_H* reuse */
+    HIP_TRY(hipSetDevice(c->device));
+    const u64 nro = n_rows + 1;
+    int rc;
+    if ((rc = ws_reserve(c, WS_HU, (total + nro + n_rows) * sizeof(u64) + 16))) return rc;
+    if ((rc = ws_reserve(c, WS_HV, n_rows + 16))) return rc;
+    if ((rc = ws_reserve(c, WS_HOUT, (2 * ck + 1 + 2 * cv) * sizeof(u64) + 16))) return rc;
+    u64 *d_vals = (u64 *)c->ws[WS_HU], *d_ro = d_vals + total, *d_ru = d_ro + nro;
+    u8 *d_keep = (u8 *)c->ws[WS_HV];
+    u64 *d_ok = (u64 *)c->ws[WS_HOUT], *d_oo = d_ok + ck, *d_ov = d_oo + ck + 1, *d_os = d_ov + cv;
+    if (total)
+        HIP_TRY(hipMemcpyAsync(d_vals, vals, total * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+    if (n_rows) {
+        HIP_TRY(hipMemcpyAsync(d_ro, row_offs, nro * sizeof(u64), hipMemcpyHostToDevice,
+                               c->stream));
+        if (row_uids)
+            HIP_TRY(hipMemcpyAsync(d_ru, row_uids, n_rows * sizeof(u64), hipMemcpyHostToDevice,
+                                   c->stream));
+        if (row_keep)
+            HIP_TRY(hipMemcpyAsync(d_keep, row_keep, n_rows, hipMemcpyHostToDevice, c->stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_ro, 0, sizeof(u64), c->stream));
+    }
+    ua_drowtr d = {};
+    d.vals = d_vals;
+    d.row_offs = d_ro;
+    d.n_rows = n_rows;
+    d.total = total;
+    d.row_uids = (row_uids && n_rows) ? d_ru : nullptr;
+    d.row_keep = (row_keep && n_rows) ? d_keep : nullptr;
+    d.flags = flags;
+    d.out_keys = out_keys ? d_ok : nullptr;
+    d.out_offs = out_keys ? d_oo : nullptr;
+    d.cap_keys = out_keys ? ck : 0;
+    d.out_vals = out_vals ? d_ov : nullptr;
+    d.out_src = out_src ? d_os : nullptr;
+    d.cap_vals = out_vals ? cv : 0;
+    u64 ng = UINT64_MAX, nt = UINT64_MAX;
+    rc = ua_rows_transpose_dev(c, &d, &ng, &nt);
+    if (rc && rc != UA_ERR_INVALID) return rc;
+    if (rc == UA_ERR_INVALID && ng == UINT64_MAX) return rc; /* rejected */
+    *n_groups = ng;
+    *out_total = nt;
+    const bool is_short = (out_keys && ng > cap_keys) || (out_vals && nt > cap_vals);
+    if (!is_short && out_keys) {
+        if (ng) HIP_TRY(hipMemcpyAsync(out_keys, d_ok, ng * sizeof(u64), hipMemcpyDeviceToHost,
+                                       c->stream));
+        HIP_TRY(hipMemcpyAsync(out_offs, d_oo, (ng + 1) * sizeof(u64), hipMemcpyDeviceToHost,
+                               c->stream));
+        if (out_vals && nt) {
+            HIP_TRY(hipMemcpyAsync(out_vals, d_ov, nt * sizeof(u64), hipMemcpyDeviceToHost,
+                                   c->stream));
+            if (out_src)
+                HIP_TRY(hipMemcpyAsync(out_src, d_os, nt * sizeof(u64), hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return is_short ? UA_ERR_INVALID : UA_OK;
 }
 
 struct ua_owned_pack {

@@ -714,6 +714,113 @@ typedef struct {
 } ua_drowsort;                  /* 13 slots, 104 bytes */
 int ua_rows_sort_dev(ua_ctx *, const ua_drowsort *, uint64_t *out_total);
 
+/* Transpose a CSR UID matrix in ONE call (since v20): given
+ * src -> [dst...], produce dst -> [src...], device resident, one sync, nothing
+ * per edge on the host.  It is the step the reference runs per edge or per
+ * element, through a hash map or a posting-list mutation:
+ *   formResult                 query/groupby.go:195-260
+ *   fillGroupedVars            query/groupby.go:265-361
+ *     uid child:   dedup.addValue(attr, uid, srcUid) per element
+ *                              query/groupby.go:104-128, :210-221, :292-298
+ *     value child: the same grouping, one element per row
+ *                              query/groupby.go:224-234, :302-312
+ *   rebuildReverseEdges        posting/index.go:1759-1791, one
+ *     addReverseMutation       posting/index.go:276-298 per posting
+ *   rebuildCountIndex          posting/index.go:1595-1640 (addCountMutation :431)
+ *   the bulk mapper's reverse entries  dgraph/cmd/bulk/mapper.go:398-432
+ *                              (x.ReverseKey at :345), sorted in reduce
+ * With it a reverse-index rebuild is ua_rows_decode[_mut]_dev ->
+ * ua_rows_transpose_dev -> ua_rows_encode_dev, and groupby over a uid
+ * predicate is one call once the child's matrix exists; count(uid) per group
+ * is the group's length.
+ *
+ *  1. An element is LIVE when its flat index i is below min(row_offs[n_rows],
+ *     total), its row is the unique r with row_offs[r] <= i < row_offs[r+1],
+ *     and row_keep is NULL or row_keep[r] != 0 (formResult's
+ *     `IndexOf(ul, srcUid) < 0 -> continue`; the caller computes the mask with
+ *     ua_index_of_batch_dev).  Every other element takes no part.
+ *  2. out_keys[0 .. *n_groups) holds the distinct values of the live elements,
+ *     ascending as unsigned 64-bit.  0 and UINT64_MAX are ordinary values.
+ *     With row_keep == NULL and row_offs[n_rows] == total this is exactly the
+ *     output of ua_rows_union_dev(vals, total).
+ *  3. Group g holds one entry per live element whose value is out_keys[g],
+ *     ordered by flat input index ascending: row ascending, then position,
+ *     which is addValue's append order.  The entry's payload is
+ *     out_vals = row_uids ? row_uids[r] : r; out_src is the flat INPUT index
+ *     (a reverse edge carries the forward posting's facets, index.go:1775).
+ *  4. out_offs[g] is the group's first entry; out_offs[*n_groups] == *out_total.
+ *  5. Multiplicity is kept by default: a uid twice in one row yields its row
+ *     twice, as addValue does.  UA_TR_UNIQUE collapses entries with the same
+ *     (value, row) to the one with the lowest flat index, because a reverse
+ *     posting list is a set.  On duplicate-free rows the two agree.
+ *  6. Rows need not be sorted.  When row_uids is ascending every group is an
+ *     ascending list, duplicate-free under UA_TR_UNIQUE or on duplicate-free
+ *     rows: valid input for ua_rows_encode_dev, ua_rows_filter_dev and a
+ *     second transpose.
+ *  7. One element per row (row_offs = 0, 1, ..., n_rows) groups the rows by a
+ *     per-row key: value-node groupby over order-independent u64 keys, or
+ *     rebuildCountIndex with vals set to the list lengths.  No extra
+ *     parameter is needed.
+ *
+ * Capacity, by the family's rule as far as it can hold with two sizes:
+ * *n_groups and *out_total are always the REQUIRED values.  Every store is
+ * bounded: keys by cap_keys, group offsets by cap_keys + 1, entries by
+ * cap_vals.  A short capacity with non-NULL outputs returns UA_ERR_INVALID,
+ * outputs untouched past the capacities.  Both requirements are at most total,
+ * so a caller may size by total and skip a count call.  Three forms: full
+ * (all outputs, out_src optional); groups only (out_vals and out_src NULL,
+ * cap_vals 0: groupby with only count(uid)); count only (all four outputs
+ * NULL, both capacities 0; no scan and no write pass run).  Group offsets are
+ * written whenever keys are.
+ *
+ * Rejected with UA_ERR_INVALID before the context is touched, nothing
+ * written: a null ctx, desc, n_groups or out_total; null vals with total > 0;
+ * null row_offs with n_rows > 0; n_rows == 0 with total != 0; unknown flag
+ * bits; out_keys and out_offs not both NULL or both non-NULL; either of them
+ * NULL with cap_keys > 0; out_vals NULL with cap_vals > 0; out_src without
+ * out_vals; out_vals without out_keys; any output overlapping an input or
+ * another output; total >= 2^31 or n_rows >= 2^31 (a flat index and the dead
+ * bit share a 32-bit tag); either capacity >= 2^60.  total == 0 and
+ * n_rows == 0 are valid: zero groups, and out_offs[0] = 0 if given.
+ *
+ * Memory safety does not depend on the data: row_offs entries are clamped to
+ * total (they are only compared against flat indices below total); with a
+ * row_offs that is not monotone an element's row is unspecified, but it is
+ * some index < n_rows that holds the element, or the element is dead; every
+ * index read back from a record is clamped below total and every row below
+ * n_rows; each input element is one record and is emitted at most once, so
+ * *out_total <= total and *n_groups <= *out_total hold for any input; barriers
+ * sit only under workgroup-uniform conditions.
+ *
+ * Engine scratch: 28 bytes per element (two buffers of an 8-byte value and a
+ * 4-byte tag, and a 4-byte row), 24 bytes per 2048-element tile (two counts
+ * and their scanned offsets), the scan partials and 16 bytes of words.
+ *
+ * Stats, with R = ceil(log2(ceil(total / 2048))): 2 + R launches for the
+ * count-only form (tile sort, R rounds, flags), 5 + R for the groups-only and
+ * the full form (two scan kernels and the write pass more), 0 for total == 0.
+ * kernel_ms is the whole sequence.  bytes_algorithmic grows by input plus
+ * stored output: 8*total for vals, 8*(n_rows+1) for row_offs, 8*n_rows for
+ * row_uids if given, n_rows for row_keep if given, 8 per stored key, 8 per
+ * stored group offset (stored keys + 1), 8 per stored entry, plus 8 per stored
+ * entry for out_src. */
+enum { UA_TR_UNIQUE = 1 };
+typedef struct {
+    const uint64_t *vals;      /* device [total]: rows concatenated */
+    const uint64_t *row_offs;  /* device [n_rows+1], non-decreasing, [0]=0 */
+    uint64_t n_rows, total;
+    const uint64_t *row_uids;  /* device [n_rows] (SrcUIDs) or NULL = the row index */
+    const uint8_t  *row_keep;  /* device [n_rows], nonzero = row takes part; NULL = all */
+    uint64_t flags;            /* UA_TR_* */
+    uint64_t *out_keys;        /* device [cap_keys]: distinct values, ascending */
+    uint64_t *out_offs;        /* device [cap_keys+1]: CSR offsets of the groups */
+    uint64_t cap_keys;
+    uint64_t *out_vals;        /* device [cap_vals]: per group, the rows' uids */
+    uint64_t *out_src;         /* optional, device [cap_vals]: flat INPUT index */
+    uint64_t cap_vals;
+} ua_drowtr;                   /* 13 slots, 104 bytes */
+int ua_rows_transpose_dev(ua_ctx *, const ua_drowtr *, uint64_t *n_groups, uint64_t *out_total);
+
 /* fused decode+intersect: algo.IntersectCompressedWith (uidlist.go:33) over a
  * device pack; v device; out device, capacity min(total_uids, m). */
 int ua_intersect_packed_dev(ua_ctx *, const ua_dpack *, uint64_t after_uid,
@@ -855,6 +962,21 @@ int ua_rows_sort(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
                  uint64_t flags, int32_t count, int32_t offset, uint64_t *out_vals,
                  uint64_t cap_vals, uint64_t *out_row_offs, uint64_t *out_src,
                  int32_t *out_ms_offs, uint64_t *out_total);
+/* The transpose of a UID matrix (dedup.addValue's grouping,
+ * query/groupby.go:104-128, 195-260, 265-361; rebuildReverseEdges,
+ * posting/index.go:1759-1791) as ONE call: host form of ua_rows_transpose_dev
+ * (since v20), same semantics, forms, capacity rule and checks.  vals,
+ * row_offs, row_uids (or NULL) and row_keep (or NULL) are host arrays,
+ * total = row_offs[n_rows]; out_keys (cap_keys), out_offs (cap_keys + 1),
+ * out_vals (cap_vals) and out_src (optional, cap_vals) are host arrays.  The
+ * device works on its own buffers, so the outputs may overlap the inputs.  On
+ * a short capacity *n_groups and *out_total are still delivered and the output
+ * arrays are left as they were. */
+int ua_rows_transpose(ua_ctx *, const uint64_t *vals, const uint64_t *row_offs,
+                      uint64_t n_rows, const uint64_t *row_uids, const uint8_t *row_keep,
+                      uint64_t flags, uint64_t *out_keys, uint64_t *out_offs,
+                      uint64_t cap_keys, uint64_t *out_vals, uint64_t *out_src,
+                      uint64_t cap_vals, uint64_t *n_groups, uint64_t *out_total);
 
 #ifdef __cplusplus
 }
